@@ -8,7 +8,13 @@ with inputs already resident in HBM.  N>1: one process per GPU (torchrun contrac
 sharded by batch row (weak scaling, per-GPU batch fixed), one RCCL gather of the waveforms to rank 0
 per step.  Rank 0 prints ONE JSON line.
 
-    python bench.py --gpus 1 --steps 10 --warmup 3
+A plain run measures the headline only: set-up, W warm-up steps, K timed steps, the result line.  `--full` adds everything
+else on top of the same headline run: the per-kernel table and roofline (HIP events around the launches), the error of the
+product scheme against fp64, the other schedule, the BASELINE.json companion shapes and precisions, the vocoder driver end to
+end and the CPU baseline.  `--dump-outputs DIR` writes what the last timed step returned as DIR/<name>.npy
+(`bench_outputs/` is ignored by git).
+
+    python bench.py --gpus 1 --steps 10 --warmup 3 [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 """
@@ -49,6 +55,30 @@ TILE_NAMES = ["conv_mfma_kernel<2,2,2,2,16,3>", "conv_mfma_kernel<1,4,2,2,16,3>"
               "resblock_split_kernel<SCH,2,8,MRF>"]  # the whole-MRF launch of the 32-channel stage
 SCHEMES = {"f16x3": ("SchF16x3", 3), "bf16x6": ("SchBf16x6", 6), "bf16": ("SchBf16", 1), "f16": ("SchF16", 1), "f32": ("-", 1)}
 MFMA16_PEAK_TFLOPS = 2500.0  # dense bf16 / fp16 MFMA peak; a split scheme spends 3 (f16x3) or 6 (bf16x6) MFMA FMAs per algorithmic fp32 FMA
+DUMP_BUDGET = 60 * 2 ** 20   # array bytes --dump-outputs writes in all (under 64 MB with the .npy headers)
+
+
+def dump_outputs(path, arrays):
+    """Write each array as <path>/<name>.npy: floating point as float32, integer and boolean as float64 (exact).  Over
+    DUMP_BUDGET in all, the largest array keeps a fixed, seeded sample of its rows (first axis), listed in <name>_rows.npy."""
+    import numpy as np
+    out = {}
+    for name, t in arrays.items():
+        x = t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t)
+        out[name] = x.astype(np.float32 if np.issubdtype(x.dtype, np.floating) else np.float64)
+    total = sum(x.nbytes for x in out.values())
+    if total > DUMP_BUDGET:
+        name = max(out, key=lambda k: out[k].nbytes)
+        x = out[name]
+        row_bytes = x.nbytes // x.shape[0]
+        keep = (DUMP_BUDGET - (total - x.nbytes)) // (row_bytes + 8)
+        if keep < 1:
+            raise SystemExit(f"bench.py: --dump-outputs cannot fit one row of {name} into {DUMP_BUDGET} bytes")
+        rows = np.sort(np.random.default_rng(0).choice(x.shape[0], int(keep), replace=False))
+        out[name], out[name + "_rows"] = x[rows], rows.astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    for name, x in out.items():
+        np.save(os.path.join(path, name + ".npy"), x)
 
 
 def tile_names(precision):
@@ -196,13 +226,18 @@ def main():
     ap.add_argument("--src-len", type=int, default=64)
     ap.add_argument("--workload", choices=["full", "vocoder"], default="full")
     ap.add_argument("--cpu-batch", type=int, default=8)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-alt", action="store_true", help="skip the extra exact-fp32 pass")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: per-kernel table and roofline, error vs fp64, the other schedule, the companion shapes "
+                         "and precisions, the vocoder driver and the CPU baseline (a plain run times the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the arrays the last timed step returned as DIR/<name>.npy (rank 0)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-alt", action="store_true", help="with --full: skip the runs beside the headline")
     ap.add_argument("--overlap", type=int, default=int(os.environ.get("PARROT_BENCH_OVERLAP", "1")),
                     help="1 (default since round 6): the headline run uses the two-stage pipeline across steps (TTE of batch i on a side HIP "
                          "stream beside the vocoder of batch i-1: the throughput schedule of SynthesisPipeline.submit / flush, every batch "
-                         "submitted inside the timed region finishes inside it); 0: one batch at a time.  The other schedule's rate is "
-                         "reported next to the headline either way (`sequential_steps` / `pipelined_steps`)")
+                         "submitted inside the timed region finishes inside it); 0: one batch at a time.  With --full the other schedule's "
+                         "rate is reported next to the headline (`sequential_steps` / `pipelined_steps`)")
     ap.add_argument("--precision", choices=["f32", "bf16x6", "f16x3", "bf16", "f16"], default=os.environ.get("PARROT_BENCH_PRECISION", "f16x3"),
                     help="product evaluation of the conv kernels for layers with >= 16 channels (fp32 data either way): f16x3 (default), "
                          "bf16x6 and f32 are parity-grade; bf16 / f16 are the single-MFMA reduced-precision operating point")
@@ -260,16 +295,15 @@ def main():
             gather_ev.append((e0, e1))
             return r
 
-        def finish(out):
+        def finish(out):  # a step's result as its caller receives it: N > 1 gathers the waveforms to rank 0 (None elsewhere)
             if out is None:
                 return None
-            return gather(out["wav"]) if world > 1 else out["wav"]
+            return dict(out, wav=gather(out["wav"])) if world > 1 else out
 
         def step():
             if overlap:  # TTE of this batch beside the vocoder of the previous one; results one call late
                 return finish(pipe.submit(batch))
-            wav = pipe(batch)["wav"] if workload == "full" else gen(code=vb["code"], spkr=vb["spkr"])
-            return gather(wav) if world > 1 else wav
+            return finish(pipe(batch) if workload == "full" else {"wav": gen(code=vb["code"], spkr=vb["spkr"])})
 
         def drain():  # every submitted batch is finished inside the region that submitted it
             return finish(pipe.flush()) if overlap else None
@@ -294,17 +328,17 @@ def main():
         # single-utterance step: measurement overhead, not work of the path (tools/step_time.py --prof shows the A/B).
         # (`profile=False`: no events at all -- latency rows such as the single utterance, whose ~130 launches take 7-40 us each)
         n_table = (2 if warmup >= 3 else 1) if profile else 0
-        wav = None
+        last = None
         for _ in range(max(warmup - n_table, 1 if warmup else 0)):
-            wav = step()
-        wav = drain() if overlap and warmup else wav
+            last = step()
+        last = drain() if overlap and warmup else last
         fence()
         table = []
         if profile:
             lib.parrot_prof_begin()
             for _ in range(n_table):
-                wav = step()
-            wav = drain() if overlap else wav
+                last = step()
+            last = drain() if overlap else last
             fence()
             table = read_rows(n_table)
             table.sort(key=lambda r: -r["ms_per_step"])
@@ -319,9 +353,9 @@ def main():
             step_ev[i][0].record()
             out = step()
             step_ev[i][1].record()
-            wav = out if out is not None else wav
+            last = out if out is not None else last
         out = drain()
-        wav = out if out is not None else wav
+        last = out if out is not None else last
         fence()
         elapsed = time.perf_counter() - t0
         run.step_ms = sorted(a_.elapsed_time(b_) for a_, b_ in step_ev)
@@ -377,7 +411,9 @@ def main():
                 r["why"] = "exact fp32 MFMA"
         rows.sort(key=lambda r: -r["ms_per_step"])
         rows.sort(key=lambda r: 0 if (timed and r["row"] == timed[0]["row"]) else 1)  # (stable: the timed-region row leads)
+        wav = last["wav"] if last is not None else None
         n_samples = world * B * (wav.shape[-1] if wav is not None else 4 * S * 320)
+        run.last = last
         del pipe, parrot, gen
         return float(t[0].item()), rows, n_samples, (cfg, h, tsd, vsd)
 
@@ -478,43 +514,50 @@ def main():
         del parrot, gen
         return out
 
-    elapsed, rows, n_samples_step, pieces = run(a.precision, a.steps, a.warmup, overlap_steps=bool(a.overlap))
+    elapsed, rows, n_samples_step, pieces = run(a.precision, a.steps, a.warmup, overlap_steps=bool(a.overlap), profile=a.full)
     gather_ms = run.gather_ms
     head_step_ms = list(run.step_ms)
+    last, run.last = run.last, None
+    if rank == 0 and a.dump_outputs:
+        # wav (B, 1, samples), plus ids / n_samples / tgt_mask / lens of the full workload; N > 1: the waveforms gathered from every
+        # rank, the rest of rank 0's own shard
+        dump_outputs(a.dump_outputs, {k: v for k, v in last.items() if v is not None})
+    del last
 
     if rank == 0:
         ms = elapsed / a.steps * 1e3
         value = n_samples_step / (ms / 1e3)
-        dom = rows[0]
-        prof = pmc_profile(dom["kernel"])
-        traffic, traffic_src = prof["traffic"], prof["source"]
-        cfg_, h_ = pieces[0], pieces[1]
-        tte_macs, voc_macs = algorithmic_macs(cfg_, h_, S, 4 * S)
-        step_flops = 2.0 * world * B * ((tte_macs if a.workload == "full" else 0) + voc_macs)
-        split = "_split" in dom["kernel"] or "resblock" in dom["kernel"]
-        n_mfma = SCHEMES[a.precision][1]
-        peak = MFMA16_PEAK_TFLOPS / n_mfma if split else FP32_MFMA_PEAK_TFLOPS
-        # what a bare fp16 MFMA stream sustains on THIS box under its power limit (random operands; the constant-operand figure
-        # shows the data dependence), per algorithmic fp32 FMA of the scheme: the practical ceiling next to the 2500 TF spec peak
-        ceil = {}
-        if split:
-            for key, shape, const in (("f16_16x16x32_random", 1, 0), ("f16_32x32x16_random", 0, 0), ("f16_16x16x32_constant", 1, 1)):
-                v_ = C.c_double()
-                _lib.check(lib.parrot_debug_mfma_ceiling(shape, const, C.byref(v_)))
-                ceil[key] = v_.value
-        roof = {"bound": "mfma", "kernel": dom["kernel"], "achieved": dom["tflops"], "peak": peak, "unit": "TFLOP/s",
-                "ceiling_probe_tflops": ({"mfma_stream": ceil, "per_fp32_fma": ceil["f16_16x16x32_random"] / n_mfma,
-                                          "frac_of_ceiling": dom["tflops"] / (ceil["f16_16x16x32_random"] / n_mfma),
-                                          "note": "parrot_debug_mfma_ceiling: bare v_mfma_f32_16x16x32_f16 stream, 2 waves/SIMD, measured in this run"}
-                                         if ceil else None),
-                "peak_note": (f"dense 16-bit MFMA peak 2500 TF / {n_mfma} MFMA(s) per algorithmic fp32 FMA ({a.precision}); the kernels are "
-                              "clock/power-limited on real data (DESIGN.md section 7)" if split else "fp32 MFMA peak"),
-                "frac": dom["tflops"] / peak, "traffic": traffic, "traffic_source": traffic_src, "traffic_box": prof["box"],
-                "mfma_busy": prof["mfma_busy"], "avg_launch_us": dom["avg_us"],
-                # the WHOLE step against the same roof: algorithmic FLOPs of the path (TTE + generator, real taps) / step time / peak
-                "step_tflops": step_flops / (ms / 1e3) / 1e12 / world, "step_frac": step_flops / (ms / 1e3) / 1e12 / world / peak,
-                "step_algorithmic_tflop": step_flops / 1e12,
-                "launches_per_step": dom["launches_per_step"], "alg_GBps": dom["alg_gbs"], "all_conv_kernels": rows}
+        if a.full:  # the per-kernel table of the headline run against the roofs
+            dom = rows[0]
+            prof = pmc_profile(dom["kernel"])
+            traffic, traffic_src = prof["traffic"], prof["source"]
+            cfg_, h_ = pieces[0], pieces[1]
+            tte_macs, voc_macs = algorithmic_macs(cfg_, h_, S, 4 * S)
+            step_flops = 2.0 * world * B * ((tte_macs if a.workload == "full" else 0) + voc_macs)
+            split = "_split" in dom["kernel"] or "resblock" in dom["kernel"]
+            n_mfma = SCHEMES[a.precision][1]
+            peak = MFMA16_PEAK_TFLOPS / n_mfma if split else FP32_MFMA_PEAK_TFLOPS
+            # what a bare fp16 MFMA stream sustains on THIS box under its power limit (random operands; the constant-operand figure
+            # shows the data dependence), per algorithmic fp32 FMA of the scheme: the practical ceiling next to the 2500 TF spec peak
+            ceil = {}
+            if split:
+                for key, shape, const in (("f16_16x16x32_random", 1, 0), ("f16_32x32x16_random", 0, 0), ("f16_16x16x32_constant", 1, 1)):
+                    v_ = C.c_double()
+                    _lib.check(lib.parrot_debug_mfma_ceiling(shape, const, C.byref(v_)))
+                    ceil[key] = v_.value
+            roof = {"bound": "mfma", "kernel": dom["kernel"], "achieved": dom["tflops"], "peak": peak, "unit": "TFLOP/s",
+                    "ceiling_probe_tflops": ({"mfma_stream": ceil, "per_fp32_fma": ceil["f16_16x16x32_random"] / n_mfma,
+                                              "frac_of_ceiling": dom["tflops"] / (ceil["f16_16x16x32_random"] / n_mfma),
+                                              "note": "parrot_debug_mfma_ceiling: bare v_mfma_f32_16x16x32_f16 stream, 2 waves/SIMD, measured in this run"}
+                                             if ceil else None),
+                    "peak_note": (f"dense 16-bit MFMA peak 2500 TF / {n_mfma} MFMA(s) per algorithmic fp32 FMA ({a.precision}); the kernels are "
+                                  "clock/power-limited on real data (DESIGN.md section 7)" if split else "fp32 MFMA peak"),
+                    "frac": dom["tflops"] / peak, "traffic": traffic, "traffic_source": traffic_src, "traffic_box": prof["box"],
+                    "mfma_busy": prof["mfma_busy"], "avg_launch_us": dom["avg_us"],
+                    # the WHOLE step against the same roof: algorithmic FLOPs of the path (TTE + generator, real taps) / step time / peak
+                    "step_tflops": step_flops / (ms / 1e3) / 1e12 / world, "step_frac": step_flops / (ms / 1e3) / 1e12 / world / peak,
+                    "step_algorithmic_tflop": step_flops / 1e12,
+                    "launches_per_step": dom["launches_per_step"], "alg_GBps": dom["alg_gbs"], "all_conv_kernels": rows}
         res = {
             "metric": "audio samples/sec (16 kHz; see config.note) + RTF, 256-unit batch-64 per GPU",
             "value": value, "unit": "samples/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": ms,
@@ -547,17 +590,17 @@ def main():
                        "note": "reference vocoder is 16 kHz / 320 samples per unit (utils/vocoder/config.json:24,32), not 22.05 kHz; "
                                "BASELINE configs[2] says single-speaker: this run uses the 10-speaker TTE (speaker_emb present, one extra "
                                "add kernel per step, parrot.py:98-99) and the multispkr vocoder -- a superset of the single-speaker work"},
-            "err_vs_fp64": product_error_vs_fp64(),
-            "roofline": roof,
             # the waveform gather's share of a step (max over ranks, CUDA events around the collective; 0 at N = 1) and what the
             # process group really is, so a scaling curve can be decomposed into compute and collective
             "gather_ms": gather_ms, "dist": pdist.dist_info(),
         }
+        if a.full:
+            res.update(err_vs_fp64=product_error_vs_fp64(), roofline=roof)
     if rank == 0:
         res["schedule"] = ("two-stage pipeline across steps: the TTE of batch i runs on a side HIP stream beside the vocoder of batch "
                            "i-1 (SynthesisPipeline.submit); every batch submitted inside the timed region is finished inside it"
                            if (a.overlap and a.workload == "full") else "one batch at a time")
-    if world == 1 and a.workload == "full" and not a.no_alt:
+    if a.full and world == 1 and a.workload == "full" and not a.no_alt:
         # the same steps under the other schedule, for reference (kernel timings of the pipelined schedule include the
         # side stream's interference, so `roofline` is only clean with one batch at a time: the default headline)
         e1, _, n1, _ = run(a.precision, a.steps, max(a.warmup, 3), overlap_steps=not a.overlap)
@@ -566,7 +609,7 @@ def main():
             "value": n1 / (ms1 / 1e3), "unit": "samples/s", "ms_per_step": ms1, "steps": a.steps,
             "schedule": "one batch at a time" if a.overlap else "TTE of batch i on a side HIP stream beside the vocoder of batch i-1 "
                         "(SynthesisPipeline.submit / flush); all submitted batches finish inside the timed region"}
-    if world == 1 and a.workload == "full" and not a.no_alt:
+    if a.full and world == 1 and a.workload == "full" and not a.no_alt:
         # BASELINE.json configs[1]: HiFi-GAN generator only, batch 32 x 256 units -- in the run's precision and, as the
         # config is worded ("fp32"), with every product on the exact fp32 MFMA
         for key, prec_ in (("vocoder_only_b32", a.precision), ("vocoder_only_b32_exact_fp32", "f32")):
@@ -585,14 +628,14 @@ def main():
         res["long_form_b8_u1500"] = long_form(a.precision, min(a.steps, 5))
         # the shipped vocoder driver, batched vs one utterance per launch chain (host post-processing included)
         res["driver_e2e"] = driver_e2e(a.precision)
-    if world == 1 and a.precision != "f32" and not a.no_alt:
+    if a.full and world == 1 and a.precision != "f32" and not a.no_alt:
         # the same workload with every product on the exact fp32 MFMA (v_mfma_f32_32x32x2_f32), for reference
         e2, rows2, n2, _ = run("f32", min(a.steps, 5), 1)
         ms2 = e2 / min(a.steps, 5) * 1e3
         res["exact_fp32_mfma"] = {"value": n2 / (ms2 / 1e3), "unit": "samples/s", "ms_per_step": ms2, "steps": min(a.steps, 5),
                                   "dominant_kernel": rows2[0]["kernel"], "dominant_tflops": rows2[0]["tflops"],
                                   "frac_of_fp32_mfma_peak": rows2[0]["tflops"] / FP32_MFMA_PEAK_TFLOPS}
-    if world == 1 and a.precision in ("f16x3", "bf16x6", "f32") and not a.no_alt:
+    if a.full and world == 1 and a.precision in ("f16x3", "bf16x6", "f32") and not a.no_alt:
         # BASELINE.json configs[2] names a bf16 vocoder: the reduced-precision operating point as a COMPANION line (never the
         # headline): fp32 TTE kernels' products and the vocoder's on ONE bf16 MFMA, fp32 accumulate / residual stream.
         # SNR vs the fp32 reference waveform: tests/test_gpu_baseline_shapes.py (>= 35.9 dB, the reference under autocast).
@@ -617,7 +660,7 @@ def main():
                                               "the vector L1 (352 KB per chunk and CU at 64 B/clk = 5.5 k clocks against 7 k clocks of MFMA) and its "
                                               "LDS fragment reads, not by either roof (DESIGN.md section 7, round 6)"}}
     if rank == 0:
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             cfg, h, tsd, vsd = pieces
             res["cpu_baseline"] = cpu_baseline(cfg, h, tsd, vsd, a.cpu_batch, S, vocab, n_spk)
             # the demo-style single utterance (BASELINE configs[0]); B=64 on the CPU would take ~45 s per pass and is

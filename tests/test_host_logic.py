@@ -215,6 +215,25 @@ def test_profile_kernel_names_fold_to_bench_rows():
         assert want in bench.tile_names("f16x3")
 
 
+def test_bench_dump_outputs_types_and_budget(tmp_path):
+    """`bench.py --dump-outputs`: floats as float32, integers / booleans as float64 with their values; over the budget the
+    largest array keeps a seeded sample of whole rows, the same rows every time, and the files stay under 64 MB."""
+    import bench
+    ids = torch.randint(0, 300, (4, 16))
+    bench.dump_outputs(str(tmp_path / "a"), {"wav": torch.randn(4, 1, 32), "ids": ids, "tgt_mask": ids > 150})
+    got = {f[:-4]: np.load(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")}
+    assert set(got) == {"wav", "ids", "tgt_mask"}
+    assert got["wav"].dtype == np.float32 and got["ids"].dtype == np.float64 and got["tgt_mask"].dtype == np.float64
+    assert np.array_equal(got["ids"], ids.numpy()) and np.array_equal(got["tgt_mask"], (ids > 150).numpy())
+    big = torch.arange(300 * 60000, dtype=torch.float32).reshape(300, 1, 60000)  # 72 MB
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), {"wav": big, "ids": ids})
+    assert sum(os.path.getsize(tmp_path / "b" / f) for f in os.listdir(tmp_path / "b")) <= 64 * 10 ** 6
+    rows = np.load(tmp_path / "b" / "wav_rows.npy")
+    assert np.array_equal(rows, np.load(tmp_path / "c" / "wav_rows.npy")) and 0 < len(rows) < 300
+    assert np.array_equal(np.load(tmp_path / "b" / "wav.npy"), big.numpy()[rows.astype(np.int64)])
+
+
 def test_resblock_dilation_lists_follow_the_reference_constructors():
     """ResBlock1 reads dilation[0..2], ResBlock2 dilation[0..1] -- literally (reference utils/vocoder/models.py:17-22,51-54):
     longer lists are cut, shorter ones raise IndexError, lists of different lengths per kernel size are accepted."""

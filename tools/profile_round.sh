@@ -9,7 +9,7 @@ mkdir -p "$OUT"
 export TMPDIR=/tmp
 # which box these counters come from (bench.py prints it beside roofline.traffic)
 { rocminfo 2>/dev/null | grep -m1 -i "Uuid:.*GPU-" | sed 's/^ *//'; rocminfo 2>/dev/null | grep -m1 -i "Marketing Name:.*MI3" | sed 's/^ *//'; rocm-smi --showuniqueid 2>/dev/null | grep -i "unique id:" | head -1; } | tr '\n' ' ' | sed 's/  */ /g' > "$OUT/${TAG}_box.txt"
-CMD="python $ROOT/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-alt"
+CMD="python $ROOT/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-alt"
 cd /tmp
 run() {  # name, rocprofv3 args...
   local name=$1; shift
@@ -25,5 +25,5 @@ run fetch --kernel-trace --pmc FETCH_SIZE
 run write --kernel-trace --pmc WRITE_SIZE
 run sq --kernel-trace --pmc SQ_BUSY_CU_CYCLES SQ_VALU_MFMA_BUSY_CYCLES SQ_WAVE_CYCLES SQ_LDS_BANK_CONFLICT
 cd "$ROOT"
-timeout 400 python bench.py > "$OUT/${TAG}_bench_n1.json" 2> "$OUT/${TAG}_bench_n1.err"
+timeout 600 python bench.py --full > "$OUT/${TAG}_bench_n1.json" 2> "$OUT/${TAG}_bench_n1.err"
 tail -c 600 "$OUT/${TAG}_bench_n1.json"

@@ -8,7 +8,7 @@ ROOT=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$ROOT/gpurun_out
 mkdir -p "$OUT"
 export TMPDIR=/tmp
-CMD="python $ROOT/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-alt ${BENCH_ARGS:-}"
+CMD="python $ROOT/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-alt ${BENCH_ARGS:-}"
 cd /tmp
 run() {
   local name=$1; shift
