@@ -105,7 +105,9 @@ __global__ __launch_bounds__(WAVES_M* WAVES_N * 64, MINW) void conv_split16_kern
             // (inline asm, not __builtin_amdgcn_raw_ptr_buffer_load_lds: the compiler orders every later ds_read behind an LDS-writing
             //  load it knows about -- a vmcnt wait in front of the CURRENT chunk's fragment reads -- and the scheduling constraints
             //  spill registers inside the K loop (round 3 measured that consumer 27 % slower than the converting kernel); hidden
-            //  in asm the loads are just eight more VMEM instructions, published by the vmcnt(0) + barrier that ends the chunk)
+            //  in asm the loads are just eight more VMEM instructions, published by the vmcnt(0) + barrier that ends the chunk.
+            //  M0 is compiler-reserved: saved and restored inside the statement; an SALU write of M0 needs one wait state before an
+            //  LDS-DMA load reads it, hence the s_nop 0 -- tests/test_oracle_reduced.py checks every such load in the built library)
             const int cbase = c * 4 * row_bytes;
             const unsigned dst = lds_base + (c & 1) * BUF_BYTES;
             static_for<ITEMS>([&](auto ic) {
@@ -115,7 +117,9 @@ __global__ __launch_bounds__(WAVES_M* WAVES_N * 64, MINW) void conv_split16_kern
                     const unsigned d = dst + pc * PIECE_BYTES + NT * i * 16;
                     const int vo = voff[i], so = cbase + soct[i] + pc * xpiece_bytes;
                     const u32x4 xd = xdesc;
-                    asm volatile("s_mov_b32 m0, %0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds" ::"s"(d), "v"(vo), "s"(xd), "s"(so) : "memory");
+                    unsigned keep;
+                    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tbuffer_load_dwordx4 %2, %3, %4 offen lds\n\ts_mov_b32 m0, %0"
+                                 : "=&s"(keep) : "s"(d), "v"(vo), "s"(xd), "s"(so) : "memory");
                 }
             });
         } else {
