@@ -255,6 +255,37 @@ int parrot_tte_encode(parrot_tte_t*, const int64_t* phones, const uint8_t* src_m
 int parrot_tte_decode(parrot_tte_t*, int32_t B, int32_t S, int32_t L, int32_t row_exact,
                       int64_t* ids, uint8_t* tgt_mask, float* logits /* nullable */,
                       void* state, size_t state_bytes, void* ws, size_t ws_bytes, void* stream);
+/* Teacher forcing: Parrot.forward(batch) with inference=False (modules/parrot.py:90-110) feeds the CALLER's durations to the length
+ * regulator (forward_duration(..., tgt_mask, dur_target), parrot.py:77-87; length_regulator(..., tgt_mask), duration.py:6-24) and
+ * decodes under the caller's target mask.  Call parrot_tte_set_durations between parrot_tte_encode and parrot_tte_decode_masked.
+ * dur (B,S) i64 device replaces the predicted durations in `state` (its prefix sums and out_len, rebuilt as the encode builds them);
+ * every position counts, padded ones included (repeat_interleave expands what it is given, duration.py:13-14); out_lens (B) i32
+ * device <- the per-row sums (L = their max, read by the caller with the transfer it makes anyway).  A negative duration sets device
+ * status 6 (torch: "repeats can not be negative"); src_len: the row-exact encode's (B) i32 (NULL after a padded-batch encode) -- a
+ * nonzero duration at s >= src_len[b] sets status 7 (a row alone has no such token).  Both are reported by
+ * parrot_tte_status_async / parrot_tte_check, not by the return value. */
+int parrot_tte_set_durations(parrot_tte_t*, const int64_t* dur, int32_t B, int32_t S, const int32_t* src_len /* nullable */,
+                             int32_t* out_lens, void* state, size_t state_bytes, void* stream);
+/* parrot_tte_decode with the caller's key mask (parrot.py:107: forward_decoder(out, ~tgt_mask)): key_mask (B,L) u8, 1 = attend, read
+ * only, is the attention mask of every decoder block; no tgt_mask is written.  Padded mode: pe[L] (parrot.py:106), pad frames leak
+ * through the k = 9 conv as in parrot_tte_decode (quirk Q7).  row_exact != 0 (after a row-exact encode): as parrot_tte_decode's
+ * row-exact mode -- pe[out_lens[b]], convs zero-padded at out_lens[b] -- with key_mask the row's own (t < max(out_lens[b], 1)).
+ * ids (B,L) i64 argmax with the tie guard, optional logits (B,L,n_codes) f32, workspace_bytes(B,S,L). */
+int parrot_tte_decode_masked(parrot_tte_t*, int32_t B, int32_t S, int32_t L, int32_t row_exact, const uint8_t* key_mask,
+                             int64_t* ids, float* logits /* nullable */, void* state, size_t state_bytes, void* ws, size_t ws_bytes,
+                             void* stream);
+/* ModelLoss.forward (modules/loss.py:5-21): CrossEntropyLoss(ignore_index = hubert_codes) of logits (N,V) f32 channel-last (the
+ * layout Parrot.forward returns, reshaped (-1, V), loss.py:16) against targets (N) i64, plus MSELoss of log_dur (n_src) f32 against
+ * log(dur + 1) (dur (n_src) i64) over src_mask (n_src) u8 (loss.py:13-14,17).  Per position a max-shifted log-sum-exp in fp32 and the
+ * first-max argmax; sums in fp64, fixed order, no value atomics: two calls agree bit for bit.  All pointers device.
+ * out (8 doubles) <- {sum nll, n_valid, n_correct (argmax == target), sum sq, n_src valid, n_bad, first bad target, 0}: a target
+ * outside [0, V) other than ignore_index counts in n_bad (torch: IndexError "Target ... is out of bounds."); losses (3 floats,
+ * nullable) <- {code + dur, code = sum nll / n_valid, dur = sum sq / n_src} in fp32 (NaN for an all-ignored batch / an empty
+ * src_mask, as torch).  ws: parrot_tte_loss_workspace_bytes(N). */
+size_t parrot_tte_loss_workspace_bytes(int32_t N);
+int parrot_tte_loss(const float* logits, const int64_t* targets, int32_t N, int32_t V, int64_t ignore_index, const float* log_dur,
+                    const int64_t* dur, const uint8_t* src_mask, int32_t n_src, double* out, float* losses /* nullable */, void* ws,
+                    size_t ws_bytes, void* stream);
 /* Device-side flags.  Synchronises `stream`, clears the flag; returns 0, PARROT_E_RANGE (a bad phone / speaker id <-> the
  * reference's Embedding IndexError) or PARROT_E_NONFINITE (NaN / inf logits at some position of the last decode: an
  * activation beyond the fp16 split scheme's range -- the ids of that call are not to be trusted). */

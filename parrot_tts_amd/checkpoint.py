@@ -13,22 +13,41 @@ from typing import Optional
 import torch
 import torch.nn as nn
 
+from .loss import ModelLoss
 from .tte import Parrot
 from .vocoder import AttrDict, CodeGenerator
 
 
 class LitParrot(nn.Module):
-    """Stand-in for the reference's LightningModule wrapper (inference.py:10-23): holds ``self.parrot``,
-    ``infer`` switches to eval mode first, ``load_from_checkpoint`` understands Lightning's layout."""
+    """Stand-in for the reference's LightningModule wrapper (inference.py:10-23, train.py:61-95): holds ``self.parrot`` and
+    ``self.loss_fn``, ``infer`` switches to eval mode first, ``validation_step`` is the reference's, ``load_from_checkpoint``
+    understands Lightning's layout."""
 
     def __init__(self, data_config, src_vocab_size, src_pad_idx):
         super().__init__()
         self.hparams = AttrDict(data_config=data_config, src_vocab_size=src_vocab_size, src_pad_idx=src_pad_idx)
         self.parrot = Parrot(data_config, src_vocab_size, src_pad_idx)
+        self.loss_fn = ModelLoss(data_config)
+        self.logged = {}  # what `log` received (Lightning is not a dependency: the values are kept under their names)
 
-    def infer(self, batch, row_exact: bool = False):
+    def forward(self, batch, inference=False):  # train.py:68-69
+        return self.parrot(batch, inference=inference)
+
+    def log(self, name, value, **kwargs):
+        self.logged[name] = value
+
+    def validation_step(self, batch, batch_idx):
+        """train.py:87-95: the teacher-forced forward and ModelLoss; returns the total loss, logs the three values."""
+        out, _, _, log_dur_preds = self.parrot(batch)
+        total_loss, code_loss, dur_loss = self.loss_fn(out, log_dur_preds, batch)
+        self.log("val_total_loss", total_loss, prog_bar=True, sync_dist=True)
+        self.log("val_code_loss", code_loss, prog_bar=True, sync_dist=True)
+        self.log("val_dur_loss", dur_loss, prog_bar=True, sync_dist=True)
+        return total_loss
+
+    def infer(self, batch, row_exact: bool = False, durations=None):
         self.eval()
-        return self.parrot.infer(batch, row_exact=row_exact)
+        return self.parrot.infer(batch, row_exact=row_exact, durations=durations)
 
     @classmethod
     def load_from_checkpoint(cls, checkpoint_path, map_location="cpu", weights_only: bool = True, **overrides):

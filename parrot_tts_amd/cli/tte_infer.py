@@ -12,7 +12,9 @@ any batch size: every row is evaluated as the reference evaluates that utterance
 per-row conv padding and key masks, exactly L_b units), so ``--batch_size 64 --row_exact`` writes the
 ``predictions.txt`` that ``--batch_size 1`` writes.  The `duration` field is the length of the
 utterance's wav in seconds (librosa in the reference, inference.py:62-63; scipy here) when that file exists, otherwise
-the duration of the emitted units (n_units / --units_per_second)."""
+the duration of the emitted units (n_units / --units_per_second).  ``--teacher_forced`` decodes each utterance from the
+durations of its val.txt ``duration`` field instead of the predicted ones (synthesis with given timing): exactly sum(duration)
+units per utterance; it combines with ``--row_exact``."""
 import argparse
 import os
 
@@ -39,6 +41,8 @@ def main(argv=None):
     ap.add_argument("--units_per_second", type=float, default=50.0)
     ap.add_argument("--row_exact", action="store_true",
                     help="evaluate every row of a padded batch as the reference evaluates that utterance alone (its driver's result)")
+    ap.add_argument("--teacher_forced", action="store_true",
+                    help="decode each utterance from its `duration` field (aligner durations) instead of the predicted ones")
     a = ap.parse_args(argv)
     cfg = yaml.load(open(a.config, "r"), Loader=yaml.FullLoader)
     ds = ParrotDataset("val", data_config=cfg)
@@ -51,7 +55,7 @@ def main(argv=None):
             idx = order[s: s + a.batch_size]
             batch = ds.collate_fn([ds[i] for i in idx])
             gpu = {k: (v.to(a.device) if isinstance(v, torch.Tensor) else v) for k, v in batch.items()}
-            rows = model.infer(gpu, row_exact=a.row_exact)
+            rows = model.infer(gpu, row_exact=a.row_exact, durations=gpu["duration"] if a.teacher_forced else None)
             for i, name, codes in zip(idx, batch["ids"], rows):
                 speaker = "_".join(name.split("_")[:2])
                 wav = os.path.join(audio_dir, speaker, "wavs", name + ".wav")

@@ -260,30 +260,212 @@ static __global__ void rebase_lens_kernel(const int32_t* __restrict__ lens, int3
     if (b < B) out[b] = min(max(lens[b] - lo, 0), n);
 }
 
-// inclusive prefix sums + totals of given durations (parrot_length_regulator: the standalone entry point)
-static __global__ __launch_bounds__(256) void dur_prefix_kernel(const int64_t* __restrict__ dur, int32_t* __restrict__ cum, int32_t* __restrict__ out_len, int S) {
-    __shared__ int32_t part[256];
+// inclusive prefix sums + totals of given (B,S) durations: parrot_length_regulator (the standalone entry point) and teacher
+// forcing (parrot_tte_set_durations: parrot.py:104, forward_duration(..., dur_target), duration.py:6-24).  Every position counts,
+// padded ones included (repeat_interleave expands whatever it is given, duration.py:13-14); a negative duration counts as 0.
+// Sums are int64, stored saturated at INT32_MAX: a row longer than max_len keeps its true length for the host's tgt_mask width
+// check (duration.py:12), and the decode's L < max_len check then fails as pe[L] does in the reference (fft.py:18).
+// err (nullable): a negative duration raises device status 6 (torch: "repeats can not be negative"); with src_len (row-exact
+// encode) a nonzero duration at s >= src_len[b] raises 7 (the row alone has no such token) and counts as 0.
+static __global__ __launch_bounds__(256) void dur_prefix_kernel(const int64_t* __restrict__ dur, int32_t* __restrict__ cum, int32_t* __restrict__ out_len, int S,
+                                                                int* __restrict__ err = nullptr, const int32_t* __restrict__ src_len = nullptr) {
+    __shared__ int64_t part[256];
     const int b = blockIdx.x, tid = threadIdx.x;
     const int per = (S + 255) / 256;
     const int s_begin = min(S, tid * per), s_end = min(S, s_begin + per);
-    int32_t local = 0;
-    for (int s = s_begin; s < s_end; ++s) local += (int32_t)max(dur[(size_t)b * S + s], (int64_t)0);
+    const int real = src_len ? src_len[b] : S;
+    auto take = [&](int s) -> int64_t {
+        const int64_t d = dur[(size_t)b * S + s];
+        if (d < 0) {
+            if (err) atomicExch(err, 6);
+            return 0;
+        }
+        if (s >= real && d != 0) {
+            if (err) atomicExch(err, 7);
+            return 0;
+        }
+        return min(d, (int64_t)INT32_MAX);  // (S * 2^31 cannot overflow int64)
+    };
+    int64_t local = 0;
+    for (int s = s_begin; s < s_end; ++s) local += take(s);
     part[tid] = local;
     __syncthreads();
     if (tid == 0) {
-        int32_t run = 0;
+        int64_t run = 0;
         for (int i = 0; i < 256; ++i) {
-            const int32_t v = part[i];
+            const int64_t v = part[i];
             part[i] = run;
             run += v;
         }
-        out_len[b] = run;
+        out_len[b] = (int32_t)min(run, (int64_t)INT32_MAX);
     }
     __syncthreads();
-    int32_t run = part[tid];
+    int64_t run = part[tid];
     for (int s = s_begin; s < s_end; ++s) {
-        run += (int32_t)max(dur[(size_t)b * S + s], (int64_t)0);
-        cum[(size_t)b * S + s] = run;
+        run += take(s);
+        cum[(size_t)b * S + s] = (int32_t)min(run, (int64_t)INT32_MAX);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// ModelLoss (modules/loss.py:5-21): CrossEntropyLoss(ignore_index) over (N, V) channel-last fp32 logits + MSELoss of the
+// log-durations over src_mask.  Stage 1: one wave per position -- max-shifted log-sum-exp in fp32, nll = log(sum) - (x[t] - max)
+// (log_softmax's order), and whether the first-max argmax is the target; each block's 16 positions are added in fp64 in row
+// order.  Stage 2 (one block): the block partials and the duration term, each thread a fixed strided slice, then a fixed LDS
+// tree.  No atomics on values: two calls agree bit for bit.  Reads the logits once (V <= 1024 and 16-byte rows: from registers).
+// ---------------------------------------------------------------------------------------------
+constexpr int LOSS_WAVES = 16;      // positions per stage-1 block
+constexpr int LOSS_CHUNKS = 4;      // float4 per lane held in registers: V <= 1024 on the vector path
+constexpr int LOSS_REDUCE = 1024;   // stage-2 threads
+struct LossCounts { int32_t n_valid, n_correct, n_bad, first_bad_row; };
+
+static __global__ __launch_bounds__(64 * LOSS_WAVES) void loss_rows_kernel(const float* __restrict__ logits, const int64_t* __restrict__ tgt,
+                                                                         int N, int V, int64_t ignore, double* __restrict__ part_nll,
+                                                                         LossCounts* __restrict__ part_cnt, int64_t* __restrict__ part_bad) {
+    __shared__ double s_nll[LOSS_WAVES];
+    __shared__ int s_st[LOSS_WAVES];  // 0 skipped, 1 valid, 2 valid and argmax == target, 3 target out of range
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int row = blockIdx.x * LOSS_WAVES + wave;  // wave-uniform: every branch below is uniform
+    int st = 0;
+    double nll = 0.0;
+    if (row < N) {
+        const float* __restrict__ x = logits + (size_t)row * V;
+        const bool vec = (V & 3) == 0 && V <= 256 * LOSS_CHUNKS && ((uintptr_t)logits & 15) == 0;
+        // (vector path: the row's loads are issued together with the target's, not behind it -- an ignored row reads its logits too)
+        float4 r[LOSS_CHUNKS];
+        if (vec) {
+#pragma unroll
+            for (int k = 0; k < LOSS_CHUNKS; ++k) {
+                const int i = (k * 64 + lane) * 4;
+                r[k] = i < V ? *reinterpret_cast<const float4*>(x + i) : make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
+            }
+        }
+        const int64_t tg = tgt[row];
+        if (tg == ignore) {
+            st = 0;
+        } else if (tg < 0 || tg >= V) {
+            st = 3;
+        } else {
+            const float xt = x[tg];
+            float m = -INFINITY, s = 0.f;
+            int mi = V;
+            if (vec) {
+#pragma unroll
+                for (int k = 0; k < LOSS_CHUNKS; ++k) {
+                    const int i = (k * 64 + lane) * 4;
+                    const float e[4] = {r[k].x, r[k].y, r[k].z, r[k].w};
+#pragma unroll
+                    for (int j = 0; j < 4; ++j)
+                        if (i + j < V && e[j] > m) { m = e[j]; mi = i + j; }
+                }
+                for (int o = 32; o > 0; o >>= 1) {  // (value, index): larger value, then smaller index -- torch.argmax's first maximum
+                    const float om = __shfl_xor(m, o);
+                    const int oi = __shfl_xor(mi, o);
+                    if (om > m || (om == m && oi < mi)) { m = om; mi = oi; }
+                }
+#pragma unroll
+                for (int k = 0; k < LOSS_CHUNKS; ++k) {
+                    const int i = (k * 64 + lane) * 4;
+                    const float e[4] = {r[k].x, r[k].y, r[k].z, r[k].w};
+#pragma unroll
+                    for (int j = 0; j < 4; ++j)
+                        if (i + j < V) s += expf(e[j] - m);
+                }
+            } else {  // any V / alignment: two passes over the row (the second from cache)
+                for (int i = lane; i < V; i += 64)
+                    if (x[i] > m) { m = x[i]; mi = i; }
+                for (int o = 32; o > 0; o >>= 1) {
+                    const float om = __shfl_xor(m, o);
+                    const int oi = __shfl_xor(mi, o);
+                    if (om > m || (om == m && oi < mi)) { m = om; mi = oi; }
+                }
+                for (int i = lane; i < V; i += 64) s += expf(x[i] - m);
+            }
+            s = wave_sum(s);
+            nll = (double)(logf(s) - (xt - m));
+            st = mi == (int)tg ? 2 : 1;
+        }
+    }
+    if (lane == 0) {
+        s_nll[wave] = nll;
+        s_st[wave] = st;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double a = 0.0;
+        LossCounts c{0, 0, 0, -1};
+        int64_t bad_t = 0;
+        for (int w = 0; w < LOSS_WAVES; ++w) {
+            a += s_nll[w];
+            c.n_valid += s_st[w] == 1 || s_st[w] == 2;
+            c.n_correct += s_st[w] == 2;
+            if (s_st[w] == 3 && c.n_bad++ == 0) {
+                c.first_bad_row = blockIdx.x * LOSS_WAVES + w;
+                bad_t = tgt[c.first_bad_row];
+            }
+        }
+        part_nll[blockIdx.x] = a;
+        part_cnt[blockIdx.x] = c;
+        part_bad[blockIdx.x] = bad_t;
+    }
+}
+
+// out[0..7] = {sum nll, n_valid, n_correct, sum sq, n_src, n_bad, first bad target, 0}; losses (nullable) = {total, code, dur} fp32
+static __global__ __launch_bounds__(LOSS_REDUCE) void loss_reduce_kernel(const double* __restrict__ part_nll, const LossCounts* __restrict__ part_cnt,
+                                                                         const int64_t* __restrict__ part_bad, int nblk,
+                                                                         const float* __restrict__ log_dur, const int64_t* __restrict__ dur,
+                                                                         const uint8_t* __restrict__ src_mask, int n_src, double* __restrict__ out,
+                                                                         float* __restrict__ losses) {
+    __shared__ double s_nll[LOSS_REDUCE], s_sq[LOSS_REDUCE];
+    __shared__ int s_valid[LOSS_REDUCE], s_correct[LOSS_REDUCE], s_bad[LOSS_REDUCE], s_src[LOSS_REDUCE];
+    __shared__ int s_first[LOSS_REDUCE];  // lowest-numbered block with an out-of-range target (nblk: none)
+    const int tid = threadIdx.x;
+    double a = 0.0, q = 0.0;
+    int nv = 0, nc = 0, nb = 0, ns = 0, first = nblk;
+    for (int i = tid; i < nblk; i += LOSS_REDUCE) {
+        const LossCounts c = part_cnt[i];
+        a += part_nll[i];
+        nv += c.n_valid;
+        nc += c.n_correct;
+        nb += c.n_bad;
+        if (c.n_bad && i < first) first = i;
+    }
+    for (int i = tid; i < n_src; i += LOSS_REDUCE) {
+        if (!src_mask[i]) continue;
+        const float d = log_dur[i] - logf((float)dur[i] + 1.0f);  // log(duration.float() + 1), loss.py:14
+        q += (double)(d * d);
+        ++ns;
+    }
+    s_nll[tid] = a; s_sq[tid] = q; s_valid[tid] = nv; s_correct[tid] = nc; s_bad[tid] = nb; s_src[tid] = ns; s_first[tid] = first;
+    __syncthreads();
+    for (int h = LOSS_REDUCE / 2; h > 0; h >>= 1) {
+        if (tid < h) {
+            s_nll[tid] += s_nll[tid + h];
+            s_sq[tid] += s_sq[tid + h];
+            s_valid[tid] += s_valid[tid + h];
+            s_correct[tid] += s_correct[tid + h];
+            s_bad[tid] += s_bad[tid + h];
+            s_src[tid] += s_src[tid + h];
+            s_first[tid] = min(s_first[tid], s_first[tid + h]);
+        }
+        __syncthreads();
+    }
+    if (tid == 0) {
+        out[0] = s_nll[0];
+        out[1] = (double)s_valid[0];
+        out[2] = (double)s_correct[0];
+        out[3] = s_sq[0];
+        out[4] = (double)s_src[0];
+        out[5] = (double)s_bad[0];
+        out[6] = s_first[0] < nblk ? (double)part_bad[s_first[0]] : 0.0;
+        out[7] = 0.0;
+        if (losses) {
+            const float code = (float)(s_nll[0] / (double)s_valid[0]);  // 0 / 0 = NaN: an all-ignored batch, as torch gives
+            const float durl = (float)(s_sq[0] / (double)s_src[0]);
+            losses[0] = code + durl;  // loss.py:19, in fp32
+            losses[1] = code;
+            losses[2] = durl;
+        }
     }
 }
 
@@ -315,7 +497,8 @@ static __global__ __launch_bounds__(256) void length_regulate_kernel(const float
     const float* __restrict__ pe_row = pe + (size_t)(row_exact ? min(len, L) : L) * (pe_stride < 0 ? D : pe_stride);  // (pe_stride 0: one row for every length)
     // (row-exact rows of length 0 keep key 0 valid: a softmax over no keys at all is 0 / 0, and its NaN would raise the batch's
     //  non-finite flag for a row that emits nothing -- the host recomputes the returned mask from the lengths)
-    if (wave == 0) tgt_mask[(size_t)b * L + t] = (row_exact ? t < max(len, 1) : t <= len) ? 1 : 0;
+    // (tgt_mask NULL: the caller supplies the decoder's key mask -- parrot_tte_decode_masked, teacher forcing)
+    if (wave == 0 && tgt_mask) tgt_mask[(size_t)b * L + t] = (row_exact ? t < max(len, 1) : t <= len) ? 1 : 0;
     int src = -1;
     if (t < len) {
         const int32_t* cb = cum + (size_t)b * S;

@@ -2090,11 +2090,14 @@ extern "C" int parrot_tte_encode(parrot_tte_t* t, const int64_t* phones, const u
 // Decode rows [row0, row0 + n) of the batch that parrot_tte_encode left in `state` (B rows).  ids / tgt_mask / logits point at the
 // group's own first row.  L is the WHOLE batch's expanded length (pe[L], parrot.py:106) whichever rows are decoded, and every
 // kernel of the decoder works row by row, so a row decoded in a group equals the same row decoded with the whole batch bit for bit.
+// key_mask (nullable, (B,L) u8 of the group's rows, read only): the caller's key mask (teacher forcing, parrot.py:104-108) replaces
+// the one the length regulator builds; tgt_mask is then not written and may be NULL.
 static int tte_decode_rows(parrot_tte_t* t, int32_t Bfull, int32_t S, int32_t L, int32_t row0, int32_t B, int64_t* ids, uint8_t* tgt_mask,
                            float* logits, void* state, size_t state_bytes, void* ws, size_t ws_bytes, void* stream, int lane, bool guard_restart,
-                           bool new_batch, bool row_exact) {
+                           bool new_batch, bool row_exact, const uint8_t* key_mask = nullptr) {
     if (lane < 0 || lane >= parrot_tte::LANES) return fail(PARROT_E_INVALID, "tte_decode: lane out of range");
-    if (!t || !ids || !tgt_mask || !state || !ws) return fail(PARROT_E_INVALID, "tte_decode: null argument");
+    if (!t || !ids || !(tgt_mask || key_mask) || !state || !ws) return fail(PARROT_E_INVALID, "tte_decode: null argument");
+    if (key_mask) tgt_mask = nullptr;
     if (Bfull <= 0 || S <= 0) return fail(PARROT_E_INVALID, "tte_decode: empty batch");
     if (row0 < 0 || B <= 0 || row0 + B > Bfull) return fail(PARROT_E_INVALID, "tte_decode: row group outside the encoded batch");
     if (L <= 0) return fail(PARROT_E_INVALID, "tte_decode: L must be > 0 (all durations zero: the reference fails in MultiheadAttention too)");
@@ -2114,6 +2117,7 @@ static int tte_decode_rows(parrot_tte_t* t, int32_t Bfull, int32_t S, int32_t L,
     t->lanes_used = (new_batch ? 0 : t->lanes_used) | (1 << lane);
     hipLaunchKernelGGL(length_regulate_kernel, dim3((L + 63) / 64, B), dim3(256), 0, s, st.enc_out + (size_t)row0 * D * S, st.cum + (size_t)row0 * S,
                        st.out_len + row0, t->pe, w.x, tgt_mask, S, L, D, t->guard > 0.f ? gstat : nullptr, guard_restart ? 1 : 0, row_exact ? 1 : 0);
+    const uint8_t* const valid = key_mask ? key_mask : tgt_mask;
     HIP_TRY(hipGetLastError());
     auto dbg = [&](size_t idx, const float* src, size_t n) -> int {
         if (idx < t->dbg_dec.size() && t->dbg_dec[idx])
@@ -2122,7 +2126,7 @@ static int tte_decode_rows(parrot_tte_t* t, int32_t Bfull, int32_t S, int32_t L,
     };
     TRY(dbg(0, w.x, (size_t)B * D * L));
     for (size_t n = 0; n < t->dec.size(); ++n) {
-        TRY(fft_block(t, t->dec[n].get(), w, w.x, tgt_mask, B, L, s, row_exact ? st.out_len + row0 : nullptr));
+        TRY(fft_block(t, t->dec[n].get(), w, w.x, valid, B, L, s, row_exact ? st.out_len + row0 : nullptr));
         TRY(dbg(1 + n, w.x, (size_t)B * D * L));
     }
     TRY(conv_launch(t->head.get(), w.x, nullptr, w.logits, B, L, EPI_STORE, 1.f, 0, 0, 0, s));
@@ -2158,6 +2162,75 @@ extern "C" int parrot_tte_decode(parrot_tte_t* t, int32_t B, int32_t S, int32_t 
         TRY(poison(logits, (size_t)B * L * t->cfg.n_codes * sizeof(float), s));
     }
     return tte_decode_rows(t, B, S, L, 0, B, ids, tgt_mask, logits, state, state_bytes, ws, ws_bytes, stream, 0, true, true, row_exact != 0);
+}
+
+// Teacher forcing (parrot.py:104, duration.py:6-24): the caller's durations replace the predicted ones in `state`
+extern "C" int parrot_tte_set_durations(parrot_tte_t* t, const int64_t* dur, int32_t B, int32_t S, const int32_t* src_len, int32_t* out_lens,
+                                        void* state, size_t state_bytes, void* stream) {
+    if (!t || !dur || !out_lens || !state) return fail(PARROT_E_INVALID, "tte_set_durations: null argument");
+    if (B <= 0 || S <= 0) return fail(PARROT_E_INVALID, "tte_set_durations: empty batch");
+    hipStream_t s = (hipStream_t)stream;
+    Arena sa(state, state_bytes);
+    TteState st = tte_state(t, sa, B, S);
+    if (!sa.ok) return fail(PARROT_E_NOMEM, "tte_set_durations: state too small");
+    if (poison_word()) TRY(poison(out_lens, (size_t)B * sizeof(int32_t), s));
+    hipLaunchKernelGGL(dur_prefix_kernel, dim3(B), dim3(256), 0, s, dur, st.cum, st.out_len, S, t->err, src_len);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(out_lens, st.out_len, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+    return PARROT_OK;
+}
+extern "C" int parrot_tte_decode_masked(parrot_tte_t* t, int32_t B, int32_t S, int32_t L, int32_t row_exact, const uint8_t* key_mask,
+                                        int64_t* ids, float* logits, void* state, size_t state_bytes, void* ws, size_t ws_bytes, void* stream) {
+    if (!t || !key_mask || !ids || !state || !ws) return fail(PARROT_E_INVALID, "tte_decode_masked: null argument");
+    if (poison_word() && B > 0 && L > 0) {
+        hipStream_t s = (hipStream_t)stream;
+        TRY(poison(ws, ws_bytes, s));
+        TRY(poison(ids, (size_t)B * L * sizeof(int64_t), s));
+        TRY(poison(logits, (size_t)B * L * t->cfg.n_codes * sizeof(float), s));
+    }
+    return tte_decode_rows(t, B, S, L, 0, B, ids, nullptr, logits, state, state_bytes, ws, ws_bytes, stream, 0, true, true, row_exact != 0,
+                           key_mask);
+}
+
+// ModelLoss (modules/loss.py:5-21): loss_rows_kernel + loss_reduce_kernel (kernels_misc.h)
+static size_t loss_ws(Arena& a, int32_t N, double** nll, LossCounts** cnt, int64_t** bad) {
+    const size_t nblk = (size_t)std::max((N + LOSS_WAVES - 1) / LOSS_WAVES, 1);
+    *nll = a.take<double>(nblk);
+    *cnt = a.take<LossCounts>(nblk);
+    *bad = a.take<int64_t>(nblk);
+    return align_up(a.off, 256);
+}
+extern "C" size_t parrot_tte_loss_workspace_bytes(int32_t N) {
+    if (N < 0) return 0;
+    Arena a(nullptr, 0);
+    double* nll;
+    LossCounts* cnt;
+    int64_t* bad;
+    return loss_ws(a, N, &nll, &cnt, &bad);
+}
+extern "C" int parrot_tte_loss(const float* logits, const int64_t* targets, int32_t N, int32_t V, int64_t ignore_index, const float* log_dur,
+                               const int64_t* dur, const uint8_t* src_mask, int32_t n_src, double* out, float* losses, void* ws, size_t ws_bytes,
+                               void* stream) {
+    if (!logits || !targets || !log_dur || !dur || !src_mask || !out || !ws) return fail(PARROT_E_INVALID, "tte_loss: null argument");
+    if (N <= 0 || V <= 0 || n_src < 0) return fail(PARROT_E_INVALID, "tte_loss: empty logits or negative size");
+    hipStream_t s = (hipStream_t)stream;
+    Arena a(ws, ws_bytes);
+    double* nll;
+    LossCounts* cnt;
+    int64_t* bad;
+    (void)loss_ws(a, N, &nll, &cnt, &bad);
+    if (!a.ok) return fail(PARROT_E_NOMEM, "tte_loss: workspace too small");
+    if (poison_word()) {
+        TRY(poison(ws, ws_bytes, s));
+        TRY(poison(out, 8 * sizeof(double), s));
+        TRY(poison(losses, 3 * sizeof(float), s));
+    }
+    const int nblk = (N + LOSS_WAVES - 1) / LOSS_WAVES;
+    hipLaunchKernelGGL(loss_rows_kernel, dim3(nblk), dim3(64 * LOSS_WAVES), 0, s, logits, targets, N, V, ignore_index, nll, cnt, bad);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(loss_reduce_kernel, dim3(1), dim3(LOSS_REDUCE), 0, s, nll, cnt, bad, nblk, log_dur, dur, src_mask, n_src, out, losses);
+    HIP_TRY(hipGetLastError());
+    return PARROT_OK;
 }
 
 extern "C" int parrot_tte_debug_stages(parrot_tte_t* t, float* const* enc_ptrs, float* const* dec_ptrs) {
@@ -2291,6 +2364,8 @@ static int read_flag(int* err, hipStream_t s, const char* who) {
     HIP_TRY(hipStreamSynchronize(s));
     if (h) {
         HIP_TRY(hipMemsetAsync(err, 0, sizeof(int), s));
+        if (h == 6) return fail(PARROT_E_INVALID, std::string(who) + ": repeats can not be negative (a negative duration, duration.py:14)");
+        if (h == 7) return fail(PARROT_E_INVALID, std::string(who) + ": row-exact durations: a nonzero duration at a padded source position");
         if (h == 5)
             return fail(PARROT_E_NONFINITE, std::string(who) + ": non-finite output (waveform sample / logits) -- an activation left the range of the fp16 split "
                                                                 "scheme (|x| < 8190); create the handle with PARROT_PREC_BF16X6 or PARROT_PREC_F32");

@@ -34,20 +34,22 @@ class SynthesisPipeline:
         mode (quirk Q2), exactly len in the row-exact mode.  (The device copy comes from the lengths the encoder left there --
         ``Parrot._run`` forms it before the decoder is enqueued: handing the host tensor over would be a pageable host-to-device
         copy, which blocks the host until the decoder has drained -- 0.2-0.3 ms of idle GPU per batch.)"""
-        if r.get("row_exact"):
+        if r.get("row_exact") or r.get("teacher_forced"):  # (teacher forcing: exactly sum(dur_b) ids)
             return r["lens"].to(torch.int64), r["emitted_dev"]
         return torch.clamp(r["lens"].to(torch.int64) + 1, max=L), r["emitted_dev"]
 
     @torch.no_grad()
-    def __call__(self, batch: Dict[str, torch.Tensor], spkr: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+    def __call__(self, batch: Dict[str, torch.Tensor], spkr: Optional[torch.Tensor] = None,
+                 durations: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
         """batch: collated TTE batch (phones, src_mask, speaker).  ``spkr`` (B,1): vocoder speaker ids
         (defaults to the TTE speaker ids).  Returns wav (B,1,hop*L), n_samples (B,) = hop*emitted ids
         per row (rows shorter than L emit len+1 ids, reference quirk Q2), ids, tgt_mask.  wav[b, :, n_samples[b]:] is
-        unspecified (padding)."""
+        unspecified (padding).  ``durations`` (B, S): synthesis with given timing (``Parrot.infer``): row b emits exactly
+        sum(dur_b) ids and is vocoded with unit_lens = sum(dur_b), n_samples = hop * sum(dur_b)."""
         # the vocoder's device flag of the PREVIOUS call (bad unit id, non-finite waveform: an activation beyond the fp16 split
         # scheme's range) is read with the TTE's length transfer: a checkpoint that leaves the range fails loudly, by default,
         # one call late and at no extra synchronisation (`check()` covers the last call)
-        r = self.parrot.infer_dense(batch, status_hooks=(self.generator._status_hook,), row_exact=self.row_exact)
+        r = self.parrot.infer_dense(batch, status_hooks=(self.generator._status_hook,), row_exact=self.row_exact, durations=durations)
         ids = r["ids"]
         if spkr is None and self.generator.multispkr:
             spkr = batch["speaker"].reshape(-1, 1)

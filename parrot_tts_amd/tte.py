@@ -2,9 +2,9 @@
 
 Same constructor ``Parrot(data_config, src_vocab_size, src_pad_idx)`` (reads
 ``<root_path>/speakers.json`` like the reference, parrot.py:24-26), same ``state_dict`` keys
-(SURVEY 8b), same ``infer(batch) -> List[List[int]]`` / ``forward(batch, inference=True)``.
-The module only holds parameters; the arithmetic runs in the HIP library.  Training forward
-(``inference=False``) is out of scope and raises."""
+(SURVEY 8b), same ``infer(batch) -> List[List[int]]`` / ``forward(batch, inference=True)``, and the teacher-forced
+``forward(batch)`` (caller durations and target mask, parrot.py:90-110) of an eval-mode model.  The module only holds
+parameters; the arithmetic runs in the HIP library.  Training (a forward in training mode, backward) is out of scope and raises."""
 from __future__ import annotations
 
 import ctypes as C
@@ -209,17 +209,23 @@ class Parrot(nn.Module):
         """Device status codes (csrc/kernels_misc.h) -> the exceptions the reference raises / this package promises."""
         if code == 0:
             return
+        if code == 6:  # parrot_tte_set_durations: torch.repeat_interleave's error (duration.py:14)
+            raise RuntimeError("repeats can not be negative")
+        if code == 7:
+            raise ValueError(f"{who}: row_exact=True durations: a nonzero duration at a padded source position (a row alone has no such token)")
         if code == 5:
             raise FloatingPointError(f"{who}: non-finite output (waveform sample / logits) -- an activation left the range of the fp16 split "
                                      "scheme (|x| < 8190); use PARROT_PRECISION=bf16x6 or f32 for this checkpoint")
         raise IndexError(f"{who}: embedding index out of range (code {code})")
 
     @torch.no_grad()
-    def _encode(self, batch, status_hooks=(), row_exact: bool = False) -> dict:
+    def _encode(self, batch, status_hooks=(), row_exact: bool = False, durations=None, key_mask=None) -> dict:
         """Phase 1 (encoder, duration predictor) and the ONE device-to-host transfer of the path (the expanded lengths: the
         reference's own host sync, duration.py:10).  ``status_hooks``: callables ``hook(dst_ptr, stream_ptr) -> name`` that enqueue a
         copy of another handle's device status flag (the vocoder's, see SynthesisPipeline): they ride on that transfer.
         ``row_exact``: every row is evaluated as the reference evaluates that utterance ALONE (see ``infer``).
+        ``durations`` (B, S): teacher forcing -- the caller's durations replace the predicted ones before the transfer (which then
+        carries their sums); ``key_mask`` (B, L): the caller's decoder key mask, checked for width and empty rows on that transfer.
         Returns the context ``_decode`` continues from."""
         phones = batch["phones"]
         require_cuda(phones, "batch['phones']")
@@ -247,9 +253,19 @@ class Parrot(nn.Module):
         log_dur = torch.empty((B, S), dtype=torch.float32, device=dev)
         dur = torch.empty((B, S), dtype=torch.int64, device=dev)
         # expanded lengths + this handle's status flag + one slot per hook: ONE device-to-host transfer fetches them all
-        status = torch.zeros((B + 2 + len(status_hooks),), dtype=torch.int32, device=dev)  # (last slot: the prefix check above)
+        # (the last two slots: the prefix check above, a key-mask row with no True entry)
+        status = torch.zeros((B + 3 + len(status_hooks),), dtype=torch.int32, device=dev)
         if row_exact:
-            status[-1:] = not_prefix
+            status[-2:-1] = not_prefix
+        if durations is not None:
+            durations = durations.to(dev, torch.int64).contiguous()
+            if tuple(durations.shape) != (B, S):
+                raise RuntimeError(f"repeats must have the same size as input along dim: durations {tuple(durations.shape)}, phones {(B, S)}")
+        if key_mask is not None:
+            key_mask = key_mask.to(dev)
+            if key_mask.dim() != 2 or key_mask.shape[0] != B:
+                raise ValueError(f"tgt_mask must be (B, L) with B = {B}, got {tuple(key_mask.shape)}")
+            status[-1:] = (~key_mask.bool().any(1)).any().to(torch.int32).reshape(1)
         lens = status[:B]
         state = torch.empty(lib.parrot_tte_state_bytes(self._handle, B, S), dtype=torch.uint8, device=dev)
         st = stream_ptr(dev)
@@ -259,6 +275,9 @@ class Parrot(nn.Module):
                 _lib.check(lib.parrot_tte_encode(self._handle, dptr(phones), dptr(valid), dptr(speaker) if speaker is not None else None,
                                                  dptr(src_len) if src_len is not None else None, B, S, dptr(log_dur), dptr(dur), dptr(lens),
                                                  dptr(state), state.numel(), dptr(ws), ws.numel(), st))
+                if durations is not None:  # (the predicted `dur` stays as it is: what the duration predictor computed)
+                    _lib.check(lib.parrot_tte_set_durations(self._handle, dptr(durations), B, S, dptr(src_len) if src_len is not None else None,
+                                                            dptr(lens), dptr(state), state.numel(), st))
                 _lib.check(lib.parrot_tte_status_async(self._handle, status.data_ptr() + 4 * B, st))
                 hooked = [hook(status.data_ptr() + 4 * (B + 1 + i), st) for i, hook in enumerate(status_hooks)]
                 hooked = [h if isinstance(h, tuple) else (h, None) for h in hooked]  # (name, on_nonfinite callback or None)
@@ -266,7 +285,7 @@ class Parrot(nn.Module):
             except _lib.ParrotHipError as e:
                 self._reraise(e)
         lens_h = status_h[:B]
-        if int(status_h[-1]):
+        if int(status_h[-2]):
             raise ValueError("row_exact=True needs src_mask to be a right-padded prefix per row (modules/data.py:97-104 pads on the right); "
                              "this mask has a pad inside an utterance or left padding -- run the padded-batch mode (row_exact=False) instead")
         # bad phone / speaker ids of THIS encode (the reference's Embedding IndexError), non-finite logits of the previous
@@ -278,6 +297,14 @@ class Parrot(nn.Module):
             if int(status_h[B + 1 + i]) == 5 and on_nonfinite is not None:
                 on_nonfinite()
             self._raise_status(int(status_h[B + 1 + i]), nm)
+        if key_mask is not None:
+            if key_mask.shape[1] != int(lens_h.max()):  # reference duration.py:11-12
+                raise AssertionError(f"tgt_mask width {key_mask.shape[1]} != max sum of durations {int(lens_h.max())} (duration.py:12)")
+            if int(status_h[-1]):
+                raise ValueError("tgt_mask has a row with no True entry: the reference's attention gives NaN for that row (torch "
+                                 "MultiheadAttention over all-masked keys); every row needs at least one target frame")
+        if durations is not None and int(lens_h.max()) >= self.max_len:  # (before the decode sizes its scratch by L)
+            raise IndexError(f"expanded length {int(lens_h.max())} >= max_len {self.max_len} (pe[T] out of range, fft.py:18)")
         return {"B": B, "S": S, "L": int(lens_h.max()), "dev": dev, "state": state, "log_dur": log_dur, "dur": dur, "lens": lens_h,
                 "lens_dev": lens, "src_mask": src_mask, "handle": self._handle, "row_exact": bool(row_exact)}
 
@@ -290,9 +317,11 @@ class Parrot(nn.Module):
         raise e
 
     @torch.no_grad()
-    def _decode(self, ctx: dict, ids: torch.Tensor, tgt: torch.Tensor, logits: Optional[torch.Tensor]) -> None:
+    def _decode(self, ctx: dict, ids: torch.Tensor, tgt: Optional[torch.Tensor], logits: Optional[torch.Tensor],
+                key_mask: Optional[torch.Tensor] = None) -> None:
         """Phase 2 of the encoded batch, on the CURRENT stream: length regulator, decoder, head, argmax (+ tie guard) into
-        ``ids`` / ``tgt`` (/ ``logits``).  The scratch buffer is allocated on the current stream."""
+        ``ids`` / ``tgt`` (/ ``logits``).  ``key_mask`` (B, L) u8: the caller's decoder key mask instead (``tgt`` unused).
+        The scratch buffer is allocated on the current stream."""
         lib = _lib.lib()
         B, S, L, dev = ctx["B"], ctx["S"], ctx["L"], ctx["dev"]
         ws = torch.empty(lib.parrot_tte_workspace_bytes(self._handle, B, S, L), dtype=torch.uint8, device=dev)
@@ -300,25 +329,39 @@ class Parrot(nn.Module):
         state.record_stream(torch.cuda.current_stream(dev))
         with torch.cuda.device(dev):
             try:
-                _lib.check(lib.parrot_tte_decode(self._handle, B, S, L, 1 if ctx["row_exact"] else 0, dptr(ids), dptr(tgt),
-                                                 dptr(logits) if logits is not None else None, dptr(state), state.numel(),
-                                                 dptr(ws), ws.numel(), stream_ptr(dev)))
+                if key_mask is not None:
+                    _lib.check(lib.parrot_tte_decode_masked(self._handle, B, S, L, 1 if ctx["row_exact"] else 0, dptr(key_mask), dptr(ids),
+                                                            dptr(logits) if logits is not None else None, dptr(state), state.numel(),
+                                                            dptr(ws), ws.numel(), stream_ptr(dev)))
+                else:
+                    _lib.check(lib.parrot_tte_decode(self._handle, B, S, L, 1 if ctx["row_exact"] else 0, dptr(ids), dptr(tgt),
+                                                     dptr(logits) if logits is not None else None, dptr(state), state.numel(),
+                                                     dptr(ws), ws.numel(), stream_ptr(dev)))
             except _lib.ParrotHipError as e:
                 self._reraise(e)
 
     @torch.no_grad()
-    def _run(self, batch, want_logits: bool, status_hooks=(), row_exact: bool = False):
-        ctx = self._encode(batch, status_hooks, row_exact=row_exact)
+    def _run(self, batch, want_logits: bool, status_hooks=(), row_exact: bool = False, durations=None, key_mask=None):
+        """``durations`` (B, S): teacher forcing.  With ``key_mask`` (B, L) the decoder attends under the caller's mask (``forward``);
+        without, under t < max(sum(dur_b), 1) -- the mask collate builds for an utterance of sum(dur_b) codes (key 0 kept for a row
+        of none, which emits nothing) -- and every row emits exactly sum(dur_b) ids."""
+        ctx = self._encode(batch, status_hooks, row_exact=row_exact, durations=durations, key_mask=key_mask)
         lib = _lib.lib()
         B, L, dev = ctx["B"], ctx["L"], ctx["dev"]
+        teacher = durations is not None
+        if teacher:
+            if key_mask is None:
+                km = (torch.arange(L, device=dev)[None, :] < ctx["lens_dev"].clamp(min=1)[:, None]).to(torch.uint8)
+            else:
+                km = key_mask.to(dev, torch.uint8).contiguous()
         ids = torch.empty((B, L), dtype=torch.int64, device=dev)
-        tgt = torch.empty((B, L), dtype=torch.uint8, device=dev)
+        tgt = None if teacher else torch.empty((B, L), dtype=torch.uint8, device=dev)
         logits = torch.empty((B, L, lib_n_codes(self)), dtype=torch.float32, device=dev) if want_logits else None
         # ids per row as `infer` returns them (len + 1 clamped to L: quirk Q2; exactly len in the row-exact mode), on the device for a
         # vocoder that follows: computed HERE, in the shadow of the length sync, so that no small kernel sits between the decoder's
         # last launch and the vocoder's first
-        emitted_dev = ctx["lens_dev"] if row_exact else torch.clamp(ctx["lens_dev"] + 1, max=L)
-        self._decode(ctx, ids, tgt, logits)
+        emitted_dev = ctx["lens_dev"] if (row_exact or teacher) else torch.clamp(ctx["lens_dev"] + 1, max=L)
+        self._decode(ctx, ids, tgt, logits, key_mask=km if teacher else None)
         if self._probe_pending:  # first decode of this handle: one synchronous look at the device flag
             self._probe_pending = False
             if self.range_fallback and int(lib.parrot_tte_precision(self._handle)) == PREC_F16X3:
@@ -329,12 +372,17 @@ class Parrot(nn.Module):
                     if int(flag.cpu()) == 5:
                         _lib.check(lib.parrot_tte_status_async(self._handle, dptr(flag), st))  # handled here: clear it
                         if self._fall_back("the first decode of this handle produced non-finite logits"):
-                            return self._run(batch, want_logits, status_hooks=(), row_exact=row_exact)
-        tgt_mask = tgt.bool()
-        if row_exact:  # a row alone is the longest of its batch: exactly `lens` ids, no extra frame (the device mask keeps one key
+                            return self._run(batch, want_logits, status_hooks=(), row_exact=row_exact, durations=durations,
+                                             key_mask=key_mask)
+        if teacher:  # the caller's mask (forward), or exactly sum(dur_b) ids per row
+            tgt_mask = key_mask.to(dev).bool() if key_mask is not None else torch.arange(L, device=dev)[None, :] < ctx["lens_dev"][:, None]
+        elif row_exact:  # a row alone is the longest of its batch: exactly `lens` ids, no extra frame (the device mask keeps one key
             tgt_mask = torch.arange(L, device=dev)[None, :] < ctx["lens_dev"][:, None]  # valid for rows of length 0)
+        else:
+            tgt_mask = tgt.bool()
         return {"ids": ids, "tgt_mask": tgt_mask, "log_dur": ctx["log_dur"], "dur": ctx["dur"], "lens": ctx["lens"], "logits": logits,
-                "src_mask": ctx["src_mask"], "lens_dev": ctx["lens_dev"], "row_exact": bool(row_exact), "emitted_dev": emitted_dev}
+                "src_mask": ctx["src_mask"], "lens_dev": ctx["lens_dev"], "row_exact": bool(row_exact), "emitted_dev": emitted_dev,
+                "teacher_forced": teacher}
 
     @torch.no_grad()
     def forward_stages(self, batch) -> dict:
@@ -406,26 +454,39 @@ class Parrot(nn.Module):
                 raise
 
     def forward(self, batch, inference=False):
-        if inference is not True:
-            raise NotImplementedError("parrot_tts_amd.Parrot implements the inference path only (training is out of scope)")
-        r = self._run(batch, want_logits=True)
-        return (r["logits"], batch["src_mask"], r["tgt_mask"], r["log_dur"])
+        """Reference modules/parrot.py:90-110.  ``inference=True``: predicted durations, the decoder's key mask t <= len (quirk Q2).
+        Otherwise the teacher-forced forward of an eval-mode model (LitParrot.validation_step, train.py:87-95): the caller's
+        ``batch["duration"]`` (B, S) expand the encoder output (every position counts, padded ones too) and ``batch["tgt_mask"]``
+        (B, max sum) is the decoder's key mask; returns (logits (B, L, V), src_mask, the caller's tgt_mask, the predicted log
+        durations).  Training mode raises: there is no backward."""
+        if inference is True:
+            r = self._run(batch, want_logits=True)
+            return (r["logits"], batch["src_mask"], r["tgt_mask"], r["log_dur"])
+        if self.training:
+            raise NotImplementedError("parrot_tts_amd.Parrot has no training forward (no backward, dropout or optimiser); call .eval() for "
+                                      "the teacher-forced forward")
+        assert "duration" in batch.keys()  # reference modules/parrot.py:92
+        r = self._run(batch, want_logits=True, durations=batch["duration"], key_mask=batch["tgt_mask"])
+        return (r["logits"], batch["src_mask"], batch["tgt_mask"], r["log_dur"])
 
-    def infer(self, batch, row_exact: bool = False) -> List[List[int]]:
+    def infer(self, batch, row_exact: bool = False, durations=None) -> List[List[int]]:
         """``Parrot.infer`` of the reference (modules/parrot.py:112-120).  Default: the reference's result for THIS padded batch
         (quirk Q7: it depends on the batch composition).  ``row_exact=True``: every row as the reference evaluates that utterance
-        alone -- what its driver, which runs batch_size = 1 (inference.py:34), writes to predictions.txt -- at batched speed."""
+        alone -- what its driver, which runs batch_size = 1 (inference.py:34), writes to predictions.txt -- at batched speed.
+        ``durations`` (B, S) int: synthesis with given timing -- the decoder expands the caller's durations instead of the
+        predicted ones, under the key mask t < sum(dur_b) that collate builds for an utterance of sum(dur_b) codes, and every row
+        emits exactly sum(dur_b) ids (both modes).  A batch's own ``duration`` entry is never used implicitly."""
         assert self.training == False  # noqa: E712  (reference modules/parrot.py:113)
-        r = self._run(batch, want_logits=False, row_exact=row_exact)
+        r = self._run(batch, want_logits=False, row_exact=row_exact, durations=durations)
         self.check_outputs()  # (infer() synchronises anyway to hand python lists back)
         ids, msk = r["ids"].cpu(), r["tgt_mask"].cpu()
         return [c[m].numpy().tolist() for c, m in zip(ids, msk)]
 
-    def infer_dense(self, batch, status_hooks=(), row_exact: bool = False) -> dict:
+    def infer_dense(self, batch, status_hooks=(), row_exact: bool = False, durations=None) -> dict:
         """Batched, device-resident result (ids (B,L), tgt_mask, lens) for pipelines that feed the vocoder
-        directly instead of going through Python lists."""
+        directly instead of going through Python lists.  ``durations``: as ``infer``."""
         assert self.training == False  # noqa: E712
-        return self._run(batch, want_logits=False, status_hooks=status_hooks, row_exact=row_exact)
+        return self._run(batch, want_logits=False, status_hooks=status_hooks, row_exact=row_exact, durations=durations)
 
 
 def lib_n_codes(m: "Parrot") -> int:
