@@ -6,7 +6,7 @@ The contract of these modes (``include/parrot_hip.h``, the ``PARROT_PREC_*`` blo
 one MFMA per product group, fp32 accumulation, fp32 outputs and residual stream.  In detail:
 
   * bf16: round-to-nearest-even of the fp32 value (``pk_bf16``, ``csrc/conv_split.h``; host weights ``bf16_rn_host``,
-    ``csrc/parrot_hip.hip``);
+    ``csrc/weight_pack.h``);
   * fp16: round-to-nearest-even after a power-of-two scale -- activations by ``XS = 8`` (``SchF16::XS``), the weights of a
     layer by ``f16_weight_scale`` (max|w| * scale in [2^14, 2^15)); overflow gives inf (``pk_f16`` / ``f16_rn_host``);
   * the layer's leaky ReLU is applied BEFORE the rounding (``pre_scale``, ``csrc/conv_split.h``), bias and residual are
@@ -78,7 +78,7 @@ def round_rtz(t: torch.Tensor, mode: str, scale: float = 1.0) -> torch.Tensor:
 
 
 def f16_weight_scale(w: torch.Tensor) -> float:
-    """``f16_weight_scale`` of csrc/parrot_hip.hip, line for line: the power of two that puts max|w| into [2^14, 2^15);
+    """``f16_weight_scale`` of csrc/weight_pack.h, line for line: the power of two that puts max|w| into [2^14, 2^15);
     1 for an all-zero or non-finite maximum."""
     mx = float(w.detach().to(torch.float32).abs().max()) if w.numel() else 0.0  # for (...) mx = max(mx, fabs(w[i]))
     if not (mx > 0.0) or not math.isfinite(mx):                                   # if (!(mx > 0.f) || !isfinite(mx)) return 1.f
@@ -120,7 +120,7 @@ def reduced_layer(kind: str, c_in: int, c_out: int, k: int, stride: int = 1, *, 
     if kind not in ("conv", "convt", "rb"):
         raise ValueError(f"unknown layer kind {kind!r}")
     transposed = kind == "convt"
-    # parrot_hip.hip voc_create_body: a ResBlock1 whose (channels, k) the pair kernels take gets a concatenated weight stream
+    # parrot_hip.hip voc_create: a ResBlock1 whose (channels, k) the pair kernels take gets a concatenated weight stream
     # (`rb_stream`, needs a split scheme), and voc_forward runs it on resblock_split_launch whenever `v->fused != 0` -- also
     # at 16 channels, where the layer plans themselves are exact (rows < 32, below)
     if kind == "rb" and fused != 0 and resblock_type == 1 and resblock_split_has(c_out, k) and 2 * n_dil <= RBS_MAX_CONVS:

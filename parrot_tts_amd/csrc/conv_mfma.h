@@ -112,16 +112,6 @@ struct ConvParams {
 // 64x into this epilogue costs ~40 VGPRs and a wave of occupancy.
 __device__ __forceinline__ float apply_act(float v, int act) { return (act == ACT_RELU && v < 0.f) ? 0.f : v; }
 
-static __global__ void tanh_inplace_kernel(float* __restrict__ y, size_t n, int* __restrict__ err) {
-    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) {
-        const float v = y[i];
-        y[i] = tanhf(v);
-        // NaN / inf reached the waveform (fp16 split range exceeded).  The PRE-activation is tested: tanhf(+-inf) = +-1 would pass
-        if (err && !(fabsf(v) < INFINITY)) atomicExch(err, 5);
-    }
-}
-
 // ---- shared by every conv kernel variant: accumulator init (bias + folded residual) and epilogue --------------
 // m_wave / n_wave: first GEMM row / column of this wave's tile block; C/D layout of the 32x32 MFMA shapes:
 // col = lane&31, row = (r&3) + 8*(r>>2) + 4*(lane>>5) (identical for the f32 and bf16 instructions).

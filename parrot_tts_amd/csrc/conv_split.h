@@ -550,8 +550,5 @@ inline hipError_t launch_conv_split(int scheme, int variant, const ConvParams& p
         default: return hipErrorInvalidValue;
     }
 }
-inline int scheme_pieces(int scheme) { return scheme == SchBf16x6::ID ? 3 : scheme == SchF16x3::ID ? 2 : 1; }
-inline bool scheme_is_f16(int scheme) { return scheme == SchF16x3::ID || scheme == SchF16::ID; }
-inline float scheme_xs(int scheme) { return scheme_is_f16(scheme) ? 8.f : 1.f; }
 
 }  // namespace parrot

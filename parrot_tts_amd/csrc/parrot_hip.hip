@@ -23,8 +23,11 @@
 #include "kernels_misc.h"
 #include "resblock_split.h"
 #include "resblock_fused.h"
+#include "weight_pack.h"
 
 using namespace parrot;
+static_assert(SchBf16x6::ID == PARROT_PREC_BF16X6 && SchF16x3::ID == PARROT_PREC_F16X3 && SchBf16::ID == PARROT_PREC_BF16 && SchF16::ID == PARROT_PREC_F16,
+              "weight_pack.h reads a scheme off its PARROT_PREC_* number");
 
 // ---------------------------------------------------------------------------------------------
 // errors
@@ -101,6 +104,29 @@ static int poison(void* p, size_t bytes, hipStream_t s) {
 // optional per-launch timing of the conv kernel (HIP events on the launch stream), aggregated per
 // tile configuration: feeds bench.py's roofline object.  Off by default.
 // ---------------------------------------------------------------------------------------------
+// A row of the table is one kernel instantiation; the numbers are the positions of bench.py's TILE_NAMES (rows 0 .. NUM_TILE_CFGS - 1:
+// conv_mfma_kernel of that tile id, then the enumerators below).
+enum ProfRow {
+    PROF_SPLIT = NUM_TILE_CFGS,          // conv_split_kernel on the block shape of exact tile 0 ...
+    PROF_SPLIT_T1,                       // ... and of exact tile 1 (PROF_SPLIT + tile id)
+    PROF_RESBLOCK_FUSED,               // resblock_fused16_kernel (and resblock_fused_kernel)
+    PROF_SPLIT_V2,                       // conv_split_kernel variant 2 (128 x 64 tile)
+    PROF_SPLIT_V3,                       // conv_split_kernel variant 3
+    PROF_RBS_32,                         // resblock_split_kernel<SCH, 2>
+    PROF_RBS_16,                         // resblock16_split_kernel
+    PROF_VALU_CONV1,                     // conv1_valu_kernel / linear1_valu_kernel (valu_kind 1)
+    PROF_VALU_CONVT,                     // convt_valu_kernel (valu_kind 2)
+    PROF_SPLIT16,                        // conv_split16_kernel, even variants
+    PROF_SPLIT16_ODD,                    // conv_split16_kernel, odd variants (the 64-row tile)
+    PROF_UNUSED,
+    PROF_SPLIT16_WIDE,                   // conv_split16_kernel variant 4 (128 x 160)
+    PROF_RBS_64,                         // resblock_split_kernel<SCH, 4>
+    PROF_RBS_128,                        // resblock_split_kernel<SCH, 8>
+    PROF_RBS_256,                        // resblock_split_kernel<SCH, 16>
+    PROF_MRF,                            // the whole-MRF launch
+    PROF_ROW_COUNT
+};
+static_assert(PROF_SPLIT_V2 == PROF_SPLIT + 3 && PROF_VALU_CONVT == PROF_VALU_CONV1 + 1 && PROF_SPLIT16_ODD == PROF_SPLIT16 + 1 && PROF_ROW_COUNT == NUM_TILE_CFGS + 17, "profiler rows follow bench.py's TILE_NAMES");
 struct ProfRec {
     hipEvent_t a, b;
     int cfg;
@@ -259,56 +285,6 @@ static int fused_mode() {
     return v;
 }
 
-static inline uint16_t f16_rn_host(float x) {  // round-to-nearest-even, overflow -> inf (what v_cvt_pk_f16_f32 does)
-    const _Float16 h = (_Float16)x;
-    uint16_t u;
-    memcpy(&u, &h, 2);
-    return u;
-}
-static inline float f16_to_f(uint16_t u) {
-    _Float16 h;
-    memcpy(&h, &u, 2);
-    return (float)h;
-}
-static inline uint16_t bf16_rn_host(float x) {
-    uint32_t u;
-    memcpy(&u, &x, 4);
-    u += 0x7fffu + ((u >> 16) & 1u);
-    return (uint16_t)(u >> 16);
-}
-static inline float bf16_to_f(uint16_t h) {
-    uint32_t u = (uint32_t)h << 16;
-    float f;
-    memcpy(&f, &u, 4);
-    return f;
-}
-
-// Split-scheme weight pieces (conv_split.h).  fp16 schemes: the layer's weights are scaled by the power of two that puts
-// max|w| into [2^14, 2^15), so the second piece of every weight that matters is a normal fp16 number.
-static float f16_weight_scale(const float* w, size_t n) {
-    float mx = 0.f;
-    for (size_t i = 0; i < n; ++i) mx = std::max(mx, std::fabs(w[i]));
-    if (!(mx > 0.f) || !std::isfinite(mx)) return 1.f;
-    int e;
-    (void)std::frexp(mx, &e);  // mx = m * 2^e, m in [0.5, 1)
-    return std::ldexp(1.f, 15 - e);  // mx * scale in [2^14, 2^15)
-}
-static void split_weight(float v, int scheme, float wscale, uint16_t (&h)[3]) {
-    h[0] = h[1] = h[2] = 0;
-    if (scheme_is_f16(scheme)) {
-        const float vs = v * wscale;
-        h[0] = f16_rn_host(vs);
-        if (scheme == PARROT_PREC_F16X3) h[1] = f16_rn_host(vs - f16_to_f(h[0]));
-        return;
-    }
-    h[0] = bf16_rn_host(v);
-    if (scheme == PARROT_PREC_BF16X6) {
-        const float r1 = v - bf16_to_f(h[0]);
-        h[1] = bf16_rn_host(r1);
-        h[2] = bf16_rn_host(r1 - bf16_to_f(h[1]));
-    }
-}
-
 static int g_num_cus = 256;  // (MI355X; refreshed from the device at the first *_create)
 static void query_device() {
     static bool done = false;
@@ -406,122 +382,61 @@ static int conv_build(parrot_conv** out, const parrot_conv_desc* d, int groups, 
     if (groups > 1 && c->Mg % t.bm) return fail(PARROT_E_UNSUPPORTED, "conv_create: rows per group must be a multiple of the tile height");
     const int CI = t.ci, QN = CI / 8;
     c->nchunks = (c->Cin + CI - 1) / CI;
-    c->n_it = c->nchunks * c->kk * QN;
-    const int mtiles = (c->M + t.bm - 1) / t.bm * (t.bm / 32);
-    const size_t nfl = ((size_t)mtiles * c->n_it + 1) * 256;  // +1 group: the kernel prefetches one past the end
-    std::vector<float> pk(nfl, 0.f);
-    const int k = d->k, Cing = c->Cin;
-    if (c->cfg == 6) {  // 16x16x4 fragments: [chunk][tap][lane][4]: row = lane&15, channel = 16*chunk + 4*e + (lane>>4)
-        c->n_it = c->nchunks * c->kk;
-        pk.assign(((size_t)c->n_it + 1) * 256, 0.f);
-        for (int ch = 0; ch < c->nchunks; ++ch)
-            for (int j = 0; j < c->kk; ++j)
-                for (int lane = 0; lane < 64; ++lane)
-                    for (int e = 0; e < 4; ++e) {
-                        const int m = lane & 15, i = ch * 16 + 4 * e + (lane >> 4);
-                        if (m < c->M && i < Cing) pk[((size_t)ch * c->kk + j) * 256 + lane * 4 + e] = w[((size_t)m * Cing + i) * k + j];
-                    }
-    } else
-    for (int mt = 0; mt < mtiles; ++mt)
-        for (int ch = 0; ch < c->nchunks; ++ch)
-            for (int j = 0; j < c->kk; ++j)
-                for (int q = 0; q < QN; ++q) {
-                    float* g = pk.data() + ((size_t)mt * c->n_it + ((size_t)ch * c->kk + j) * QN + q) * 256;
-                    for (int lane = 0; lane < 64; ++lane)
-                        for (int e = 0; e < 4; ++e) {
-                            const int m = mt * 32 + (lane & 31);
-                            const int i = ch * CI + 8 * q + 2 * e + (lane >> 5);
-                            float v = 0.f;
-                            if (m < c->M && i < Cing) {
-                                if (d->transposed) {
-                                    const int o = m / c->u, r = m % c->u;
-                                    const int kap = r + d->padding - (j + dmin) * c->u;
-                                    if (kap >= 0 && kap < k) v = w[((size_t)i * d->c_out + o) * k + kap];
-                                } else {
-                                    v = w[((size_t)m * Cing + i) * k + j];
-                                }
-                            }
-                            g[lane * 4 + e] = v;
-                        }
-                }
-    // weight accessor shared by both packings: W'(m, i, j) of the GEMM view (0 outside the real extents)
-    auto wval = [&](int m, int i, int j) -> float {
-        if (m >= c->M || i >= Cing) return 0.f;
-        if (d->transposed) {
-            const int o = m / c->u, r = m % c->u;
-            const int kap = r + d->padding - (j + dmin) * c->u;
-            return (kap >= 0 && kap < k) ? w[((size_t)i * d->c_out + o) * k + kap] : 0.f;
-        }
-        return w[((size_t)m * Cing + i) * k + j];
-    };
+    c->n_it = c->cfg == 6 ? c->nchunks * c->kk : c->nchunks * c->kk * QN;
+    const int kk = c->kk;
+    const GemmWeights W{w, c->M, c->Cin, d->k, d->transposed != 0, d->c_out, c->u, d->padding, dmin};
     const int want_prec = (d->precision >= 0) ? d->precision : create_prec();
     if (want_prec > PARROT_PREC_F16) return fail(PARROT_E_INVALID, "conv_create: unknown precision");
     // split kernels: at 32 rows the exact kernel is as fast (measured); the slab fetch needs whole 16-channel chunks
     // and evaluates the leaky ReLU as max(v, slope * v).  Everything else runs on the exact kernel (same results class).
     const bool slope_ok = d->pre_act != PRE_LRELU || (d->pre_slope >= 0.f && d->pre_slope <= 1.f);
     if (want_prec >= 1 && c->Mg >= 32 && d->tile_cfg < 0 && c->Cin % 16 == 0 && slope_ok) {
-        // split plan: 16 channels per chunk, one MFMA k-step per tap; [m_tile][chunk*tap][piece][lane][8]
+        // split plan: one MFMA k-step per (chunk, tap); [row tile][chunk*tap][piece][lane][8]
         c->prec = want_prec;
-        const int NP = scheme_pieces(want_prec);
-        const bool f16 = scheme_is_f16(want_prec);
         c->cfg = (c->Mg <= 32) ? 2 : (c->Mg <= 64) ? 1 : 0;  // exact-kernel tile ids with the same block shapes
         const TileCfg t16 = tile_cfg(c->cfg);
         if (groups > 1 && c->Mg % t16.bm) return fail(PARROT_E_UNSUPPORTED, "conv_create: rows per group must be a multiple of the tile height");
-        if (f16) c->wscale = f16_weight_scale(w, (size_t)d->c_in / groups * d->c_out * d->k);
-        // wide plain convs: the 16x16x32 kernel (conv_split16.h): 32-channel chunks, [m16 tile][chunk*tap][piece][lane][8]
+        if (scheme_is_f16(want_prec)) c->wscale = f16_weight_scale(w, (size_t)d->c_in / groups * d->c_out * d->k);
+        // wide plain convs: the 16x16x32 kernel (conv_split16.h): 16-row tiles, 32-channel chunks; else 32-row tiles, 16-channel chunks
         c->mfma16 = allow16 && mfma16_enabled() && split16_has(want_prec, c->kk) && !d->transposed && groups == 1 && c->Cin % 32 == 0 && c->M >= 64;
-        size_t n16 = 0;
-        std::vector<uint16_t> pk16;
+        int rows = 32, bm = t16.bm;
         if (c->mfma16) {
-            int bm16, bn16;
-            split16_tile(c->M >= 128 ? 0 : 1, bm16, bn16);
-            c->nchunks = c->Cin / 32;
-            c->n_it16 = c->nchunks * c->kk;
-            const int mt = (c->M + bm16 - 1) / bm16 * (bm16 / 16);
-            const size_t step_h = (size_t)NP * 512;
-            n16 = ((size_t)mt * c->n_it16 + 1) * step_h;
-            if (n16 * sizeof(uint16_t) >= ((size_t)1 << 31)) return fail(PARROT_E_UNSUPPORTED, "conv_create: packed weight stream larger than 2 GiB");
-            pk16.assign(n16, 0);
-            for (int m16 = 0; m16 < mt; ++m16)
-                for (int ch = 0; ch < c->nchunks; ++ch)
-                    for (int j = 0; j < c->kk; ++j) {
-                        uint16_t* g = pk16.data() + ((size_t)m16 * c->n_it16 + (size_t)ch * c->kk + j) * step_h;
-                        for (int lane = 0; lane < 64; ++lane)
-                            for (int e = 0; e < 8; ++e) {
-                                uint16_t h[3];
-                                split_weight(wval(m16 * 16 + (lane & 15), ch * 32 + 8 * (lane >> 4) + e, j), want_prec, c->wscale, h);
-                                for (int pc = 0; pc < NP; ++pc) g[pc * 512 + lane * 8 + e] = h[pc];
-                            }
-                    }
-        } else {
-        c->nchunks = (c->Cin + 15) / 16;
-        c->n_it16 = c->nchunks * c->kk;
-        const int mt16 = (c->M + t16.bm - 1) / t16.bm * (t16.bm / 32);
-        const size_t step_h = (size_t)NP * 512;  // 16-bit words per step: NP pieces x 64 lanes x 8
-        n16 = ((size_t)mt16 * c->n_it16 + 1) * step_h;  // (+1 pad step)
-        if (n16 * sizeof(uint16_t) >= ((size_t)1 << 31)) return fail(PARROT_E_UNSUPPORTED, "conv_create: packed weight stream larger than 2 GiB");
-        pk16.assign(n16, 0);
-        for (int mt = 0; mt < mt16; ++mt)
-            for (int ch = 0; ch < c->nchunks; ++ch)
-                for (int j = 0; j < c->kk; ++j) {
-                    uint16_t* g = pk16.data() + ((size_t)mt * c->n_it16 + (size_t)ch * c->kk + j) * step_h;
-                    for (int lane = 0; lane < 64; ++lane)
-                        for (int e = 0; e < 8; ++e) {
-                            uint16_t h[3];
-                            split_weight(wval(mt * 32 + (lane & 31), ch * 16 + 8 * (lane >> 5) + e, j), want_prec, c->wscale, h);
-                            for (int pc = 0; pc < NP; ++pc) g[pc * 512 + lane * 8 + e] = h[pc];
-                        }
-                }
+            int bn16;
+            rows = 16;
+            split16_tile(c->M >= 128 ? 0 : 1, bm, bn16);
         }
-        HIP_TRY(hipMalloc((void**)&c->wfrag16, n16 * sizeof(uint16_t)));
-        HIP_TRY(hipMemcpy(c->wfrag16, pk16.data(), n16 * sizeof(uint16_t), hipMemcpyHostToDevice));
+        const int chans = 512 / rows;  // channels of a chunk: 8 per lane group
+        c->nchunks = (c->Cin + chans - 1) / chans;
+        c->n_it16 = c->nchunks * c->kk;
+        const size_t n_steps = (size_t)((c->M + bm - 1) / bm * (bm / rows)) * c->n_it16;
+        const size_t n16 = (n_steps + 1) * scheme_pieces(want_prec) * 512;  // (+1 pad step: the kernels prefetch one past the end)
+        if (n16 * sizeof(uint16_t) >= ((size_t)1 << 31)) return fail(PARROT_E_UNSUPPORTED, "conv_create: packed weight stream larger than 2 GiB");
+        std::vector<uint16_t> pk16(n16, 0);
+        const int n_it16 = c->n_it16;
+        // step = (row tile, chunk, tap); lane: row = lane % rows, channels 8 * (lane / rows) .. + 7 of the chunk
+        pack_pieces(pk16.data(), n_steps, want_prec, c->wscale, W, [=](size_t st, int lane, int e) {
+            const int mt = (int)(st / n_it16), ch = (int)(st % n_it16) / kk, j = (int)(st % n_it16) % kk;
+            return WeightAt{mt * rows + lane % rows, ch * chans + 8 * (lane / rows) + e, j};
+        });
+        HIP_TRY(hipMalloc((void**)&c->wfrag16, pk16.size() * sizeof(uint16_t)));
+        HIP_TRY(hipMemcpy(c->wfrag16, pk16.data(), pk16.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
     } else {
+        const size_t n_steps = c->cfg == 6 ? (size_t)c->n_it : (size_t)((c->M + t.bm - 1) / t.bm * (t.bm / 32)) * c->n_it;
+        std::vector<float> pk((n_steps + 1) * 256, 0.f);  // +1 group: the kernel prefetches one past the end
+        if (c->cfg == 6)  // 16x16x4 fragments, step = (chunk, tap): row = lane&15, channel = 16*chunk + 4*e + (lane>>4)
+            pack_f32(pk.data(), n_steps, W, [=](size_t st, int lane, int e) { return WeightAt{lane & 15, (int)st / kk * 16 + 4 * e + (lane >> 4), (int)st % kk}; });
+        else {  // 32x32x2 fragments, step = (32-row tile, chunk, tap, channel octet q): row = lane&31, channel = CI*chunk + 8*q + 2*e + (lane>>5)
+            const int n_it = c->n_it;
+            pack_f32(pk.data(), n_steps, W, [=](size_t st, int lane, int e) {
+                const int mt = (int)(st / n_it), r = (int)(st % n_it), q = r % QN, j = r / QN % kk, ch = r / QN / kk;
+                return WeightAt{mt * 32 + (lane & 31), ch * CI + 8 * q + 2 * e + (lane >> 5), j};
+            });
+        }
         HIP_TRY(hipMalloc((void**)&c->wfrag, pk.size() * sizeof(float)));
         HIP_TRY(hipMemcpy(c->wfrag, pk.data(), pk.size() * sizeof(float), hipMemcpyHostToDevice));
     }
     // the two narrowest vocoder layers stream through plain fp32 FMA kernels (conv_valu.h) in either precision mode
-    const bool slope01 = d->pre_act != PRE_LRELU || (d->pre_slope >= 0.f && d->pre_slope <= 1.f);
-    if (d->tile_cfg < 0 && groups == 1 && slope01 && d->dilation == 1 && valu_kernels_enabled()) {
+    if (d->tile_cfg < 0 && groups == 1 && slope_ok && d->dilation == 1 && valu_kernels_enabled()) {
         if (!d->transposed && d->c_out == 1 && ((d->k == 7 && d->padding == 3) || (d->k == 1 && d->padding == 0)) &&
             (d->act == ACT_NONE || d->act == ACT_TANH))
             c->valu_kind = 1;  // conv_post; the duration predictor's Linear(256 -> 1)
@@ -552,25 +467,35 @@ struct PlaneArgs {
 // can layer `c` take its input from / write its output to an operand plane?  (conv_split16 plans of the MRF: k = 7 / 11)
 static bool plane_ok(const parrot_conv* c) { return c && c->mfma16 && c->prec >= 1 && (c->kk == 7 || c->kk == 11) && c->M % 16 == 0 && c->Cin % 32 == 0; }
 static size_t plane_row_bytes(int prec, int C, int T) { return (size_t)(prec == PARROT_PREC_F16X3 ? 2 : 1) * 2 * C * T; }
+// Ragged batches: row b holds len[b] real units = len[b] * mul + add samples at the current layer (row_true_len, conv_mfma.h); every
+// layer applies its zero padding at the row's own end.  len == nullptr: dense rows.
+struct RowLens {
+    const int32_t* len = nullptr;
+    int mul = 1, add = 0;
+};
+// what only some callers of conv_launch pass
+struct ConvOpts {
+    RowLens rows;
+    PlaneArgs planes;
+};
 
-// x_bstride / y_bstride / res_bstride in elements; <= 0 means dense.
-static int conv_launch(const parrot_conv* c, const float* x, const float* res, float* y, int B, int Tin, int epi, float div,
-                       long x_bstride, long y_bstride, long res_bstride, hipStream_t s, const int32_t* row_len = nullptr,
-                       int row_len_mul = 1, int row_len_add = 0, const PlaneArgs* pl = nullptr) {
+static int conv_launch(const parrot_conv* c, const float* x, const float* res, float* y, int B, int Tin, int epi, float div, hipStream_t s,
+                       const ConvOpts& o = ConvOpts()) {
+    const PlaneArgs& pl = o.planes;
     if (B <= 0 || Tin <= 0) return fail(PARROT_E_INVALID, "conv_run: empty batch or sequence");
     const int Tout = c->out_len(Tin);
     if (Tout <= 0) return fail(PARROT_E_INVALID, "conv_run: sequence shorter than the kernel");
-    if (c->valu_kind && !res && epi == EPI_STORE && x_bstride <= 0 && y_bstride <= 0 && (double)c->d.c_in * Tin * 4.0 < 2147483648.0) {
+    if (c->valu_kind && !res && epi == EPI_STORE && (double)c->d.c_in * Tin * 4.0 < 2147483648.0) {
         ConvValuParams q{};
         q.x = x; q.w = c->wraw; q.bias = c->bias; q.y = y;
         q.B = B; q.Cin = c->d.c_in; q.Tin = Tin; q.Tout = Tout;
         q.slope = c->d.pre_act == PRE_LRELU ? c->d.pre_slope : 1.f;
         q.act = c->d.act;
-        q.row_len = row_len; q.row_len_mul = row_len_mul; q.row_len_add = row_len_add;
+        q.row_len = o.rows.len; q.row_len_mul = o.rows.mul; q.row_len_add = o.rows.add;
         q.err = c->err_flag;
         ProfRec rec{};
         const double macs = (double)B * c->d.c_out * c->d.c_in * c->d.k * (c->d.transposed ? (double)Tin : (double)Tout);
-        if (g_prof_on) TRY(prof_open(rec, NUM_TILE_CFGS + 6 + c->valu_kind, 2.0 * macs, 4.0 * B * ((double)c->d.c_in * Tin + (double)c->d.c_out * Tout), s));
+        if (g_prof_on) TRY(prof_open(rec, c->valu_kind == 1 ? PROF_VALU_CONV1 : PROF_VALU_CONVT, 2.0 * macs, 4.0 * B * ((double)c->d.c_in * Tin + (double)c->d.c_out * Tout), s));
         if (c->valu_kind == 1 && c->d.k == 7 && (Tin & 3) == 0 && (reinterpret_cast<size_t>(x) & 15) == 0 && (reinterpret_cast<size_t>(y) & 15) == 0)
             hipLaunchKernelGGL(conv1_valu7_vec_kernel, dim3((Tout + 1023) / 1024, B), dim3(256), 0, s, q);
         else if (c->valu_kind == 1 && c->d.k == 7) hipLaunchKernelGGL(conv1_valu_kernel<7>, dim3((Tout + 1023) / 1024, B), dim3(256), 0, s, q);
@@ -590,21 +515,21 @@ static int conv_launch(const parrot_conv* c, const float* x, const float* res, f
     p.pre = c->d.pre_act; p.pre_slope = c->d.pre_slope; p.act = c->d.act;
     p.epi = epi; p.div = div; p.u = c->u; p.u_inv16 = (65536 + c->u - 1) / c->u;
     p.groups = c->groups; p.Mg = c->Mg;
-    p.row_len = row_len; p.row_len_mul = row_len_mul; p.row_len_add = row_len_add;
+    p.row_len = o.rows.len; p.row_len_mul = o.rows.mul; p.row_len_add = o.rows.add;
     p.acc_scale = p.out_scale = 1.f;
     p.lean = 1;  // conv_split_kernel: the buffer-addressed prologue / epilogue instantiations for plain convs (conv_lean_ok)
     p.n_cus = g_num_cus;
     p.fold_res = c->late_res ? 0 : 1;
-    if (pl && (pl->xplane || pl->yplane)) {
-        if (!plane_ok(c) || (pl->yplane && epi != EPI_STORE)) return fail(PARROT_E_INVALID, "conv_run: operand planes need a conv_split16 layer (k = 7 / 11) and EPI_STORE");
-        p.xplane = pl->xplane; p.yplane = pl->yplane;
+    if (pl.xplane || pl.yplane) {
+        if (!plane_ok(c) || (pl.yplane && epi != EPI_STORE)) return fail(PARROT_E_INVALID, "conv_run: operand planes need a conv_split16 layer (k = 7 / 11) and EPI_STORE");
+        p.xplane = pl.xplane; p.yplane = pl.yplane;
         p.xplane_bstride = (long)plane_row_bytes(c->prec, c->Cin, Tin);
         p.yplane_bstride = (long)plane_row_bytes(c->prec, c->M, Tout);
-        p.yplane_slope = pl->yslope; p.plane_only = pl->plane_only;
+        p.yplane_slope = pl.yslope; p.plane_only = pl.plane_only;
     }
-    p.x_bstride = x_bstride > 0 ? x_bstride : (long)c->d.c_in * Tin;
-    p.y_bstride = y_bstride > 0 ? y_bstride : (long)c->Cout * Tout;
-    p.res_bstride = res_bstride > 0 ? res_bstride : p.y_bstride;
+    p.x_bstride = (long)c->d.c_in * Tin;  // (dense batch rows)
+    p.y_bstride = (long)c->Cout * Tout;
+    p.res_bstride = p.y_bstride;
     int cfg = c->cfg;
     if (c->prec == 0 && (cfg == 0 || cfg == 3) && p.Ncols <= 64 && tile_cfg(4).ci == tile_cfg(cfg).ci) cfg = 4;  // same packing, narrower tile
     if (c->prec >= 1) {
@@ -654,8 +579,8 @@ static int conv_launch(const parrot_conv* c, const float* x, const float* res, f
         // algorithmic work of the layer (real taps only; DESIGN.md "roofline accounting")
         const double macs = (double)B * c->d.c_out * c->Cin * c->d.k * (c->d.transposed ? (double)Tin : (double)Tout);
         const double elems = (double)B * ((double)c->d.c_in * Tin + (double)c->Cout * Tout * (1 + (res ? 1 : 0) + (epi != EPI_STORE ? 1 : 0)));
-        const int row = c->mfma16 ? (variant16 == 4 ? NUM_TILE_CFGS + 12 : NUM_TILE_CFGS + 9 + (variant16 & 1))
-                                  : (c->prec >= 1) ? (variant16 >= 2 ? NUM_TILE_CFGS + 1 + variant16 : NUM_TILE_CFGS + cfg) : cfg;  // split rows follow the exact ones
+        const int row = c->mfma16 ? (variant16 == 4 ? PROF_SPLIT16_WIDE : (variant16 & 1) ? PROF_SPLIT16_ODD : PROF_SPLIT16)
+                                  : (c->prec >= 1) ? (variant16 == 2 ? PROF_SPLIT_V2 : variant16 == 3 ? PROF_SPLIT_V3 : PROF_SPLIT + cfg) : cfg;  // (exact kernels: row = tile id)
         TRY(prof_open(rec, row, 2.0 * macs, 4.0 * (elems + (double)c->d.c_out * c->Cin * c->d.k), s));
     }
     HIP_TRY(c->mfma16 ? launch_conv_split16(c->prec, variant16, p, s) : c->prec >= 1 ? launch_conv_split(c->prec, variant16, p, s) : (cfg == 6 ? launch_conv_mfma16(p, s) : launch_conv(cfg, p, s)));
@@ -680,7 +605,7 @@ extern "C" int parrot_conv_run(parrot_conv_t* c, const float* x, const float* re
     if (epilogue < 0 || epilogue > 2) return fail(PARROT_E_INVALID, "conv_run: bad epilogue");
     if (epilogue == EPI_STORE && y != x && y != res && c->out_len(T_in) > 0)
         TRY(poison(y, (size_t)B * c->Cout * c->out_len(T_in) * sizeof(float), (hipStream_t)stream));
-    return conv_launch(c, x, res, y, B, T_in, epilogue, div, 0, 0, 0, (hipStream_t)stream);
+    return conv_launch(c, x, res, y, B, T_in, epilogue, div, (hipStream_t)stream);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -738,7 +663,7 @@ struct parrot_voc {
     struct StreamSet {
         hipStream_t side[PARROT_MAX_KERNELS] = {};
         hipEvent_t ev_fork = nullptr, ev_last[PARROT_MAX_KERNELS] = {};
-    } ss[1];
+    } ss;
     // chunk lanes of the chunk-streamed forward (lane 0 is the caller's stream)
     static constexpr int MAX_LANES = 4;
     hipStream_t lane_stream[MAX_LANES] = {};
@@ -791,13 +716,11 @@ struct parrot_voc {
     ~parrot_voc() {
         for (Graph& g : graphs) g.release();
         if (cap_stream) (void)hipStreamDestroy(cap_stream);
-        for (StreamSet& q : ss) {
-            for (hipStream_t st : q.side)
-                if (st) (void)hipStreamDestroy(st);
-            if (q.ev_fork) (void)hipEventDestroy(q.ev_fork);
-            for (hipEvent_t e : q.ev_last)
-                if (e) (void)hipEventDestroy(e);
-        }
+        for (hipStream_t st : ss.side)
+            if (st) (void)hipStreamDestroy(st);
+        if (ss.ev_fork) (void)hipEventDestroy(ss.ev_fork);
+        for (hipEvent_t e : ss.ev_last)
+            if (e) (void)hipEventDestroy(e);
         for (hipStream_t st : lane_stream)
             if (st) (void)hipStreamDestroy(st);
         if (ev_lane_fork) (void)hipEventDestroy(ev_lane_fork);
@@ -812,6 +735,22 @@ struct parrot_voc {
         if (err) (void)hipFree(err);
     }
     int chan(int stage) const { return cfg.upsample_initial_channel >> (stage + 1); }
+    // rb holds the ResBlock convs of (stage, kernel j) back to back: per_rb() convs from rb_base(stage, j)
+    int per_rb() const { return (cfg.resblock_type == 1 ? 2 : 1) * cfg.n_dil; }
+    int rb_base(int stage, int j) const { return (stage * cfg.n_kernels + j) * per_rb(); }
+    // columns either side of an output column that branch (stage, j) reads: sum over its convs of (k - 1) / 2 * dilation
+    int branch_reach(int stage, int j) const {
+        int H = 0;
+        for (int q = 0; q < per_rb(); ++q) H += (cfg.resblock_kernel_sizes[j] - 1) / 2 * rb[rb_base(stage, j) + q]->dil;
+        return H;
+    }
+    int stage_reach(int stage) const {  // the widest branch of the stage
+        int H = 0;
+        for (int j = 0; j < cfg.n_kernels; ++j) H = std::max(H, branch_reach(stage, j));
+        return H;
+    }
+    size_t branch(int stage, int j) const { return (size_t)stage * cfg.n_kernels + j; }  // index of rb_stream / rb_conv_halves
+    uint16_t* branch_stream(int stage, int j) const { return rb_stream[branch(stage, j)]; }
 };
 
 static int upload(float** dst, const float* src, size_t n) {
@@ -831,21 +770,8 @@ static int make_conv(std::unique_ptr<parrot_conv>& slot, int cin, int cout, int 
     return PARROT_OK;
 }
 
-static int voc_create_impl(parrot_voc_t** out, const parrot_voc_cfg* cfg, const parrot_voc_weights* w, int prec, int fused);
-extern "C" int parrot_voc_create(parrot_voc_t** out, const parrot_voc_cfg* cfg, const parrot_voc_weights* w) {
-    return voc_create_impl(out, cfg, w, -1, -1);
-}
-extern "C" int parrot_voc_create_ex(parrot_voc_t** out, const parrot_voc_cfg* cfg, const parrot_voc_weights* w, int32_t precision,
-                                    int32_t fused_resblocks) {
-    if (precision > PARROT_PREC_F16 || fused_resblocks > 2) return fail(PARROT_E_INVALID, "voc_create_ex: precision in -1 .. 4, fused_resblocks in -1 .. 2");
-    return voc_create_impl(out, cfg, w, precision, fused_resblocks);
-}
-static int voc_create_body(parrot_voc_t** out, const parrot_voc_cfg* cfg, const parrot_voc_weights* w);
-static int voc_create_impl(parrot_voc_t** out, const parrot_voc_cfg* cfg, const parrot_voc_weights* w, int prec, int fused) {
+static int voc_create(parrot_voc_t** out, const parrot_voc_cfg* cfg, const parrot_voc_weights* w, int prec, int fused) {
     CreateScope scope(prec, fused, -1);  // (thread-local: the process defaults are not touched)
-    return voc_create_body(out, cfg, w);
-}
-static int voc_create_body(parrot_voc_t** out, const parrot_voc_cfg* cfg, const parrot_voc_weights* w) {
     if (!out || !cfg || !w) return fail(PARROT_E_INVALID, "voc_create: null argument");
     if (cfg->n_stages <= 0 || cfg->n_stages > PARROT_MAX_STAGES || cfg->n_kernels <= 0 || cfg->n_kernels > PARROT_MAX_KERNELS ||
         cfg->n_dil <= 0 || cfg->n_dil > PARROT_MAX_DIL || (cfg->resblock_type != 1 && cfg->resblock_type != 2))
@@ -854,10 +780,10 @@ static int voc_create_body(parrot_voc_t** out, const parrot_voc_cfg* cfg, const 
     // model_in_dim - in_dim input channels come from the caller's extra conditioning streams (parrot_voc_forward_feats)
     if (cfg->model_in_dim < in_dim) return fail(PARROT_E_INVALID, "voc_create: model_in_dim smaller than embedding_dim * (1 + multispkr)");
     if ((cfg->upsample_initial_channel >> cfg->n_stages) < 1) return fail(PARROT_E_INVALID, "voc_create: too many stages for upsample_initial_channel");
-    const int per_rb = (cfg->resblock_type == 1 ? 2 : 1) * cfg->n_dil;
-    if (w->n_rb != cfg->n_stages * cfg->n_kernels * per_rb) return fail(PARROT_E_INVALID, "voc_create: wrong number of resblock convs");
     std::unique_ptr<parrot_voc> v(new parrot_voc());
     v->cfg = *cfg;
+    const int per_rb = v->per_rb();
+    if (w->n_rb != cfg->n_stages * cfg->n_kernels * per_rb) return fail(PARROT_E_INVALID, "voc_create: wrong number of resblock convs");
     query_device();
     v->scheme = create_prec();
     v->fused = create_fused();
@@ -877,11 +803,9 @@ static int voc_create_body(parrot_voc_t** out, const parrot_voc_cfg* cfg, const 
         v->mrf_auto = (e == nullptr);
         v->mrf_streams = (on && cfg->n_kernels > 1) ? cfg->n_kernels : 1;
         if (v->mrf_streams > 1) {
-            for (parrot_voc::StreamSet& q : v->ss) {
-                for (int j = 1; j < v->mrf_streams; ++j) HIP_TRY(hipStreamCreateWithFlags(&q.side[j], hipStreamNonBlocking));
-                HIP_TRY(hipEventCreateWithFlags(&q.ev_fork, hipEventDisableTiming));
-                for (int j = 0; j < v->mrf_streams; ++j) HIP_TRY(hipEventCreateWithFlags(&q.ev_last[j], hipEventDisableTiming));
-            }
+            for (int j = 1; j < v->mrf_streams; ++j) HIP_TRY(hipStreamCreateWithFlags(&v->ss.side[j], hipStreamNonBlocking));
+            HIP_TRY(hipEventCreateWithFlags(&v->ss.ev_fork, hipEventDisableTiming));
+            for (int j = 0; j < v->mrf_streams; ++j) HIP_TRY(hipEventCreateWithFlags(&v->ss.ev_last[j], hipEventDisableTiming));
         }
         for (int l = 1; l < parrot_voc::MAX_LANES; ++l) {
             HIP_TRY(hipStreamCreateWithFlags(&v->lane_stream[l], hipStreamNonBlocking));
@@ -918,7 +842,7 @@ static int voc_create_body(parrot_voc_t** out, const parrot_voc_cfg* cfg, const 
             const bool a16 = !(v->fused != 0 && cfg->resblock_type == 1 && resblock_split_has(cout, rk) && per_rb <= RBS_MAX_CONVS);
             for (int m = 0; m < cfg->n_dil; ++m) {
                 const int dl = cfg->resblock_dilation_sizes[j][m];
-                const int base = (i * cfg->n_kernels + j) * per_rb;
+                const int base = v->rb_base(i, j);
                 if (cfg->resblock_type == 1) {
                     TRY(make_conv(v->rb[base + 2 * m], cout, cout, rk, dl, (rk * dl - dl) / 2, 0, 1, PRE_LRELU, 0.1f, ACT_NONE,
                                   w->rb_w[base + 2 * m], w->rb_b[base + 2 * m], 1, a16));
@@ -943,10 +867,10 @@ static int voc_create_body(parrot_voc_t** out, const parrot_voc_cfg* cfg, const 
         for (int j = 0; j < cfg->n_kernels; ++j) {
             const int rk = cfg->resblock_kernel_sizes[j], C = v->chan(i);
             if (cfg->resblock_type != 1 || !resblock_split_has(C, rk) || per_rb > RBS_MAX_CONVS) continue;
-            const int base = (i * cfg->n_kernels + j) * per_rb;
+            const int base = v->rb_base(i, j);
             const int steps = resblock_split_steps(C, rk);
             const size_t step_b = (size_t)NP * 1024, conv_b = (size_t)steps * step_b;
-            v->rb_conv_halves[(size_t)i * cfg->n_kernels + j] = conv_b / 2;
+            v->rb_conv_halves[v->branch(i, j)] = conv_b / 2;
             if (C >= 32) {  // the plans' streams are already [row tile][chunk * k + tap]
                 bool ok = true;
                 for (int q = 0; q < per_rb; ++q) {
@@ -959,7 +883,7 @@ static int voc_create_body(parrot_voc_t** out, const parrot_voc_cfg* cfg, const 
                 //  whole conv of padding keeps that inside the allocation)
                 uint16_t* st = nullptr;
                 HIP_TRY(hipMalloc((void**)&st, (per_rb + 1) * conv_b));
-                v->rb_stream[(size_t)i * cfg->n_kernels + j] = st;
+                v->rb_stream[v->branch(i, j)] = st;
                 for (int q = 0; q <= per_rb; ++q)
                     HIP_TRY(hipMemcpy(reinterpret_cast<char*>(st) + q * conv_b, v->rb[base + (q < per_rb ? q : 0)]->wfrag16, conv_b, hipMemcpyDeviceToDevice));
                 for (int q = 0; q < per_rb; ++q) v->rb_wsc[base + q] = v->rb[base + q]->wscale;
@@ -967,24 +891,16 @@ static int voc_create_body(parrot_voc_t** out, const parrot_voc_cfg* cfg, const 
                 const size_t step_h = (size_t)NP * 512;
                 std::vector<uint16_t> pk(((size_t)per_rb * steps + 2) * step_h, 0);
                 for (int q = 0; q < per_rb; ++q) {
-                    const float* wq = w->rb_w[base + q];  // (16, 16, rk)
-                    const float wsc = scheme_is_f16(v->scheme) ? f16_weight_scale(wq, (size_t)16 * 16 * rk) : 1.f;
+                    const GemmWeights W{w->rb_w[base + q], 16, 16, rk, false, 0, 1, 0, 0};  // (16, 16, rk)
+                    const float wsc = scheme_is_f16(v->scheme) ? f16_weight_scale(W.w, (size_t)16 * 16 * rk) : 1.f;
                     v->rb_wsc[base + q] = wsc;
-                    for (int st = 0; st < steps; ++st) {
-                        uint16_t* g = pk.data() + ((size_t)q * steps + st) * step_h;
-                        for (int lane = 0; lane < 64; ++lane)
-                            for (int e = 0; e < 8; ++e) {
-                                const int row = lane & 15, ch = 8 * ((lane >> 4) & 1) + e, tap = 2 * st + (lane >> 5);
-                                const float val = tap < rk ? wq[((size_t)row * 16 + ch) * rk + tap] : 0.f;
-                                uint16_t h[3];
-                                split_weight(val, v->scheme, wsc, h);
-                                for (int pc = 0; pc < NP; ++pc) g[pc * 512 + lane * 8 + e] = h[pc];
-                            }
-                    }
+                    pack_pieces(pk.data() + (size_t)q * steps * step_h, steps, v->scheme, wsc, W, [](size_t st, int lane, int e) {
+                        return WeightAt{lane & 15, 8 * ((lane >> 4) & 1) + e, 2 * (int)st + (lane >> 5)};
+                    });
                 }
                 uint16_t* st = nullptr;
                 HIP_TRY(hipMalloc((void**)&st, pk.size() * sizeof(uint16_t)));
-                v->rb_stream[(size_t)i * cfg->n_kernels + j] = st;
+                v->rb_stream[v->branch(i, j)] = st;
                 HIP_TRY(hipMemcpy(st, pk.data(), pk.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
             }
         }
@@ -998,16 +914,8 @@ static int voc_create_body(parrot_voc_t** out, const parrot_voc_cfg* cfg, const 
             const int C = v->chan(i);
             if (cfg->resblock_type != 1 || !resblock_mrf_has(C) || per_rb > RBS_MAX_CONVS || cfg->n_kernels > RBS_MAX_BRANCH) continue;
             bool ok = true;
-            int Hmax = 0;
-            for (int j = 0; j < cfg->n_kernels; ++j) {
-                const int rk = cfg->resblock_kernel_sizes[j];
-                const int base = (i * cfg->n_kernels + j) * per_rb;
-                ok = ok && (rk & 1) && v->rb_stream[(size_t)i * cfg->n_kernels + j];
-                int H = 0;
-                for (int q = 0; q < per_rb; ++q) H += (rk - 1) / 2 * v->rb[base + q]->dil;
-                Hmax = std::max(Hmax, H);
-            }
-            v->mrf_ok[i] = ok && rbs_mrf_window(C) - 2 * Hmax >= rbs_mrf_window(C) / 2;
+            for (int j = 0; j < cfg->n_kernels; ++j) ok = ok && (cfg->resblock_kernel_sizes[j] & 1) && v->branch_stream(i, j);
+            v->mrf_ok[i] = ok && rbs_mrf_window(C) - 2 * v->stage_reach(i) >= rbs_mrf_window(C) / 2;
         }
     }
     // final F.leaky_relu(x) uses the DEFAULT slope 0.01 (models.py:107, quirk Q5)
@@ -1015,6 +923,12 @@ static int voc_create_body(parrot_voc_t** out, const parrot_voc_cfg* cfg, const 
     v->conv_post->err_flag = v->err;  // a non-finite waveform sample (an activation left the fp16 split range) raises the handle's flag
     *out = v.release();
     return PARROT_OK;
+}
+extern "C" int parrot_voc_create(parrot_voc_t** out, const parrot_voc_cfg* cfg, const parrot_voc_weights* w) { return voc_create(out, cfg, w, -1, -1); }
+extern "C" int parrot_voc_create_ex(parrot_voc_t** out, const parrot_voc_cfg* cfg, const parrot_voc_weights* w, int32_t precision,
+                                    int32_t fused_resblocks) {
+    if (precision > PARROT_PREC_F16 || fused_resblocks > 2) return fail(PARROT_E_INVALID, "voc_create_ex: precision in -1 .. 4, fused_resblocks in -1 .. 2");
+    return voc_create(out, cfg, w, precision, fused_resblocks);
 }
 extern "C" void parrot_voc_destroy(parrot_voc_t* v) { delete v; }
 extern "C" int parrot_voc_precision(const parrot_voc_t* v) { return v ? v->scheme : PARROT_E_INVALID; }
@@ -1060,46 +974,50 @@ static bool resblock_fusable(const parrot_voc* v, int stage, int j) {
     const int C = v->chan(stage), k = c.resblock_kernel_sizes[j];
     const int fm = v->fused;
     if (fm == 0 || !(C == 16 || (C == 32 && fm == 1)) || !(k & 1)) return false;
-    const int per_rb = (c.resblock_type == 1 ? 2 : 1) * c.n_dil;
+    const int per_rb = v->per_rb(), base = v->rb_base(stage, j);
     if (per_rb > RB_MAX_CONVS) return false;
-    int H = 0;
-    for (int m = 0; m < c.n_dil; ++m) {
-        const int reach = (k - 1) / 2 * c.resblock_dilation_sizes[j][m];
-        if (reach > RB_PAD) return false;
-        H += reach + (c.resblock_type == 1 ? (k - 1) / 2 : 0);
-    }
-    const int base = (stage * c.n_kernels + j) * per_rb;
+    for (int m = 0; m < c.n_dil; ++m)
+        if ((k - 1) / 2 * c.resblock_dilation_sizes[j][m] > RB_PAD) return false;
     for (int q = 0; q < per_rb; ++q)
         if (v->rb[base + q]->prec != 0 || v->rb[base + q]->cfg != (C == 16 ? 6 : 2) || !v->rb[base + q]->wfrag) return false;
-    return resblock_window(C) - 2 * H >= 128;
+    return resblock_window(C) - 2 * v->branch_reach(stage, j) >= 128;
 }
-static int resblock_fused_launch(const parrot_voc* v, int stage, int j, const float* x, float* y, int B, int T, int epi, float div,
-                                 hipStream_t s, const int32_t* row_len, int row_len_mul, int row_len_add, hipEvent_t before_last = nullptr) {
+// One ResBlock branch of an MRF stage: y (epi: =, +=, or += then / div) ResBlock_j(x) on stream s.  mid / res_a / res_b: the branch's
+// scratch tensors (between the convs of a pair; the running residual, alternating); before_last: the event the launch that accumulates into y waits for (the MRF sum runs in branch order).
+struct Branch {
+    const float* x;
+    float* y;
+    float *mid, *res_a, *res_b;
+    int B, T, epi;
+    float div;
+    hipStream_t s;
+    RowLens rows;
+    hipEvent_t before_last;
+};
+static int resblock_fused_launch(const parrot_voc* v, int stage, int j, const Branch& br) {
+    const int B = br.B, T = br.T;
     const parrot_voc_cfg& c = v->cfg;
-    const int per_rb = (c.resblock_type == 1 ? 2 : 1) * c.n_dil;
-    const int base = (stage * c.n_kernels + j) * per_rb;
+    const int per_rb = v->per_rb(), base = v->rb_base(stage, j);
     ResblockParams p{};
-    p.x = x; p.y = y;
+    p.x = br.x; p.y = br.y;
     p.n_conv = per_rb; p.type = c.resblock_type;
     p.k = c.resblock_kernel_sizes[j]; p.C = v->chan(stage); p.T = T; p.B = B;
-    p.epi = epi; p.div = div; p.slope = 0.1f;
-    p.row_len = row_len; p.row_len_mul = row_len_mul; p.row_len_add = row_len_add;
-    int H = 0;
+    p.epi = br.epi; p.div = br.div; p.slope = 0.1f;
+    p.row_len = br.rows.len; p.row_len_mul = br.rows.mul; p.row_len_add = br.rows.add;
     double macs = 0;
     for (int q = 0; q < per_rb; ++q) {
         const parrot_conv* pc = v->rb[base + q].get();
         p.wfrag[q] = pc->wfrag; p.bias[q] = pc->bias; p.dil[q] = pc->dil;
-        H += (p.k - 1) / 2 * pc->dil;
         macs += (double)B * p.C * p.C * p.k * T;
     }
-    p.H = H;
-    p.TT = resblock_window(p.C) - 2 * H;
+    p.H = v->branch_reach(stage, j);
+    p.TT = resblock_window(p.C) - 2 * p.H;
     p.tiles = (T + p.TT - 1) / p.TT;
     ProfRec rec{};
-    if (before_last) HIP_TRY(hipStreamWaitEvent(s, before_last, 0));
-    if (g_prof_on) TRY(prof_open(rec, NUM_TILE_CFGS + 2, 2.0 * macs, 4.0 * B * (double)p.C * T * (2 + (epi != EPI_STORE ? 1 : 0)), s));
-    HIP_TRY(launch_resblock_fused(p, s));
-    if (g_prof_on) TRY(prof_close(rec, s));
+    if (br.before_last) HIP_TRY(hipStreamWaitEvent(br.s, br.before_last, 0));
+    if (g_prof_on) TRY(prof_open(rec, PROF_RESBLOCK_FUSED, 2.0 * macs, 4.0 * B * (double)p.C * T * (2 + (br.epi != EPI_STORE ? 1 : 0)), br.s));
+    HIP_TRY(launch_resblock_fused(p, br.s));
+    if (g_prof_on) TRY(prof_close(rec, br.s));
     return PARROT_OK;
 }
 
@@ -1107,16 +1025,15 @@ static int resblock_fused_launch(const parrot_voc* v, int stage, int j, const fl
 // stays <= hmax columns per side (a 384-column window keeps >= 84 % of its columns at hmax = 30); every launch but
 // the last stores its running residual to a scratch buffer.
 constexpr int RBS_HMAX = 30;
-static int resblock_split_launch(const parrot_voc* v, int stage, int j, const float* x, float* y, float* tmp_a, float* tmp_b, int B, int T,
-                                 int epi, float div, hipStream_t s, const int32_t* row_len, int row_len_mul, int row_len_add,
-                                 hipEvent_t before_last = nullptr) {
+static int resblock_split_launch(const parrot_voc* v, int stage, int j, const Branch& br) {
+    const int B = br.B, T = br.T;
+    hipStream_t s = br.s;
     const parrot_voc_cfg& c = v->cfg;
-    const int per_rb = 2 * c.n_dil, k = c.resblock_kernel_sizes[j], C = v->chan(stage);
-    const int base = (stage * c.n_kernels + j) * per_rb;
-    const int W = resblock_split_window(C), steps = resblock_split_steps(C, k);
+    const int per_rb = v->per_rb(), base = v->rb_base(stage, j), k = c.resblock_kernel_sizes[j], C = v->chan(stage);
+    const int W = resblock_split_window(C);
     const int hmax = RBS_HMAX * W / RBS_W;  // the same fraction of the window
-    const uint16_t* stream = v->rb_stream[(size_t)stage * c.n_kernels + j];
-    const float* src = x;
+    const uint16_t* stream = v->branch_stream(stage, j);
+    const float* src = br.x;
     int m0 = 0, n_launch = 0;
     while (m0 < per_rb) {
         int m1 = m0, H = 0;
@@ -1129,8 +1046,8 @@ static int resblock_split_launch(const parrot_voc* v, int stage, int j, const fl
         const bool last = (m1 == per_rb);
         ResblockSplitParams p{};
         p.x = src;
-        p.y = last ? y : ((n_launch & 1) ? tmp_b : tmp_a);
-        p.wstream = stream + (size_t)m0 * v->rb_conv_halves[(size_t)stage * c.n_kernels + j];
+        p.y = last ? br.y : ((n_launch & 1) ? br.res_b : br.res_a);
+        p.wstream = stream + (size_t)m0 * v->rb_conv_halves[v->branch(stage, j)];
         p.n_conv = m1 - m0;
         p.early = 1;
         for (int q = m0; q < m1; ++q) {
@@ -1143,15 +1060,15 @@ static int resblock_split_launch(const parrot_voc* v, int stage, int j, const fl
         p.TT = W - 2 * H;
         if (p.TT < 32) return fail(PARROT_E_UNSUPPORTED, "resblock: receptive field too wide for the fused window");
         p.tiles = (T + p.TT - 1) / p.TT;
-        p.epi = last ? epi : EPI_STORE;
-        p.div = div; p.slope = 0.1f;
-        p.row_len = row_len; p.row_len_mul = row_len_mul; p.row_len_add = row_len_add;
+        p.epi = last ? br.epi : EPI_STORE;
+        p.div = br.div; p.slope = 0.1f;
+        p.row_len = br.rows.len; p.row_len_mul = br.rows.mul; p.row_len_add = br.rows.add;
         ProfRec rec{};
         const double macs = (double)B * C * C * k * T * (m1 - m0);
-        if (last && before_last) HIP_TRY(hipStreamWaitEvent(s, before_last, 0));  // the MRF sum is accumulated in branch order
+        if (last && br.before_last) HIP_TRY(hipStreamWaitEvent(s, br.before_last, 0));  // the MRF sum is accumulated in branch order
         // rows: one per kernel instantiation (C = 32 / 64 / 128 / 256 are resblock_split_kernel<SCH, 2 / 4 / 8 / 16>)
-        const int prow = C == 16 ? 6 : C == 32 ? 5 : C == 64 ? 13 : C == 128 ? 14 : 15;
-        if (g_prof_on) TRY(prof_open(rec, NUM_TILE_CFGS + prow, 2.0 * macs, 4.0 * B * (double)C * T * (2 + (p.epi != EPI_STORE ? 1 : 0)), s));
+        const ProfRow prow = C == 16 ? PROF_RBS_16 : C == 32 ? PROF_RBS_32 : C == 64 ? PROF_RBS_64 : C == 128 ? PROF_RBS_128 : PROF_RBS_256;
+        if (g_prof_on) TRY(prof_open(rec, prow, 2.0 * macs, 4.0 * B * (double)C * T * (2 + (p.epi != EPI_STORE ? 1 : 0)), s));
         HIP_TRY(launch_resblock_split(v->scheme, C, p, s));
         if (g_prof_on) TRY(prof_close(rec, s));
         src = p.y;
@@ -1163,40 +1080,29 @@ static int resblock_split_launch(const parrot_voc* v, int stage, int j, const fl
 
 // output columns per window of a whole-MRF launch of this stage (window minus twice the widest branch's total reach)
 static int mrf_tile_cols(const parrot_voc* v, int stage) {
-    const parrot_voc_cfg& c = v->cfg;
-    const int per_rb = 2 * c.n_dil;
-    int Hmax = 0;
-    for (int j = 0; j < c.n_kernels; ++j) {
-        int H = 0;
-        for (int q = 0; q < per_rb; ++q) H += (c.resblock_kernel_sizes[j] - 1) / 2 * v->rb[(stage * c.n_kernels + j) * per_rb + q]->dil;
-        Hmax = std::max(Hmax, H);
-    }
-    return std::max(1, rbs_mrf_window(v->chan(stage)) - 2 * Hmax);
+    return std::max(1, rbs_mrf_window(v->chan(stage)) - 2 * v->stage_reach(stage));
 }
 // Whole-MRF launch of the 32-channel stage (resblock_split.h, MRF instantiations): y = sum_j ResBlock_j(x) / n_kernels.
-static int mrf_split_launch(const parrot_voc* v, int stage, const float* x, float* y, int B, int T, hipStream_t s, const int32_t* row_len,
-                            int row_len_mul, int row_len_add) {
+static int mrf_split_launch(const parrot_voc* v, int stage, const float* x, float* y, int B, int T, hipStream_t s, const RowLens& rows) {
     const parrot_voc_cfg& c = v->cfg;
-    const int per_rb = 2 * c.n_dil, C = v->chan(stage), nk = c.n_kernels;
+    const int per_rb = v->per_rb(), C = v->chan(stage), nk = c.n_kernels;
     const int W = rbs_mrf_window(C);
     ResblockSplitParams p{};
     p.x = x; p.y = y;
     p.n_conv = per_rb; p.n_branch = nk;
-    int Hmax = 0, early = 1;
+    const int Hmax = v->stage_reach(stage);
+    int early = 1;
     double macs = 0;
     for (int j = 0; j < nk; ++j) {
-        const int base = (stage * nk + j) * per_rb, k = c.resblock_kernel_sizes[j];
-        p.bstream[j] = v->rb_stream[(size_t)stage * nk + j];
+        const int base = v->rb_base(stage, j), k = c.resblock_kernel_sizes[j];
+        p.bstream[j] = v->branch_stream(stage, j);
         p.bk[j] = k;
-        int H = 0;
         for (int q = 0; q < per_rb; ++q) {
             p.bias[j * per_rb + q] = v->rb[base + q]->bias;
             p.wsc[j * per_rb + q] = v->rb_wsc[base + q];
             p.dil[j * per_rb + q] = v->rb[base + q]->dil;
-            H += (k - 1) / 2 * v->rb[base + q]->dil;
             if ((k - 1) / 2 * v->rb[base + q]->dil > 32) early = 0;
         }
-        Hmax = std::max(Hmax, H);
         macs += (double)B * C * C * k * T * per_rb;
     }
     p.k = p.bk[0];
@@ -1206,9 +1112,9 @@ static int mrf_split_launch(const parrot_voc* v, int stage, const float* x, floa
     p.tiles = (T + p.TT - 1) / p.TT;
     p.epi = nk > 1 ? EPI_ADD_DIV : EPI_STORE;
     p.div = (float)nk; p.slope = 0.1f;
-    p.row_len = row_len; p.row_len_mul = row_len_mul; p.row_len_add = row_len_add;
+    p.row_len = rows.len; p.row_len_mul = rows.mul; p.row_len_add = rows.add;
     ProfRec rec{};
-    if (g_prof_on) TRY(prof_open(rec, NUM_TILE_CFGS + 16, 2.0 * macs, 4.0 * B * (double)C * T * 2, s));
+    if (g_prof_on) TRY(prof_open(rec, PROF_MRF, 2.0 * macs, 4.0 * B * (double)C * T * 2, s));
     HIP_TRY(launch_mrf_split(v->scheme, C, p, s));
     if (g_prof_on) TRY(prof_close(rec, s));
     return PARROT_OK;
@@ -1241,13 +1147,7 @@ static int voc_receptive_units(const parrot_voc* v) {
         long lo = base * hop + ph, hi = lo;
         lo -= 3; hi += 3;  // conv_post (k = 7)
         for (int i = c.n_stages - 1; i >= 0; --i) {
-            long reach = 0;  // widest ResBlock of the stage: sum over its convs of (k - 1) / 2 * dilation
-            for (int j = 0; j < c.n_kernels; ++j) {
-                const long hk = (c.resblock_kernel_sizes[j] - 1) / 2;
-                long r = 0;
-                for (int m = 0; m < c.n_dil; ++m) r += hk * c.resblock_dilation_sizes[j][m] + (c.resblock_type == 1 ? hk : 0);
-                reach = std::max(reach, r);
-            }
+            const long reach = v->stage_reach(i);  // the widest ResBlock of the stage
             lo -= reach; hi += reach;
             const long u = c.upsample_rates[i], k = c.upsample_kernel_sizes[i], p = (k - u) / 2;
             // output tau depends on inputs t with tau = t u - p + kappa, kappa in [0, k): t in [ceil((tau + p - k + 1) / u), floor((tau + p) / u)]
@@ -1263,7 +1163,7 @@ extern "C" int parrot_voc_receptive_units(const parrot_voc_t* v) { return v ? vo
 
 static int voc_forward_impl(parrot_voc_t* v, const int64_t* code, int code_stride, const int64_t* spkr, const float* feats,
                             int32_t n_feat_channels, const int32_t* unit_lens, int32_t B, int32_t U, float* wav_out,
-                            float* const* stage_out, void* ws, size_t ws_bytes, void* stream, int ns_sized = 0, int lane = 0);
+                            float* const* stage_out, void* ws, size_t ws_bytes, void* stream, int ns_sized = 0);
 
 // Small forwards through the graph cache (see parrot_voc::Graph); everything else -- and every failure of the graph path -- direct.
 static int voc_forward_graphed(parrot_voc_t* v, const int64_t* code, int code_stride, const int64_t* spkr, const float* feats,
@@ -1520,7 +1420,7 @@ extern "C" int parrot_voc_forward_chunked(parrot_voc_t* v, const int64_t* code, 
         }
         // (the branch-stream count the lane's workspace was sized for)
         TRY(voc_forward_impl(v, code + lo, U, spkr, nullptr, 0, unit_lens ? lens[lane] : nullptr, B, n, tmp[lane], nullptr, inner_ws[lane], inner,
-                             (void*)sl, ns_chunk, lane));
+                             (void*)sl, ns_chunk));
         HIP_TRY(hipMemcpy2DAsync(wav_out + (size_t)start * hop, (size_t)U * hop * sizeof(float), tmp[lane] + (size_t)(start - lo) * hop,
                                  (size_t)n * hop * sizeof(float), (size_t)(stop - start) * hop * sizeof(float), B, hipMemcpyDeviceToDevice, sl));
     }
@@ -1528,9 +1428,83 @@ extern "C" int parrot_voc_forward_chunked(parrot_voc_t* v, const int64_t* code, 
     return PARROT_OK;
 }
 
+// debug: max |conv input| per layer group (parrot_voc_debug_absmax)
+static int voc_amax(const parrot_voc* v, int group, const float* src, size_t n, hipStream_t q) {
+    if (v->dbg_absmax) {
+        hipLaunchKernelGGL(absmax_kernel, dim3((unsigned)std::min<size_t>((n + 255) / 256, 2048)), dim3(256), 0, q, src, n, v->dbg_absmax + group);
+        HIP_TRY(hipGetLastError());
+    }
+    return PARROT_OK;
+}
+
+// A ResBlock branch layer by layer: one conv launch per layer, the running residual alternating between res_a and res_b.
+static int resblock_layers_launch(const parrot_voc* v, int stage, int j, const Branch& br) {
+    const parrot_voc_cfg& c = v->cfg;
+    const int base = v->rb_base(stage, j), nd = c.n_dil, B = br.B, T = br.T;
+    const size_t n_act = (size_t)B * v->chan(stage) * T;
+    ConvOpts o;
+    o.rows = br.rows;
+    // Operand planes (conv_split16.h; PARROT_PLANES=0 switches them off): the tensor between the two convs of a pair
+    // exists only as the second conv's ready-made operand -- written once by the first conv's epilogue, the same
+    // bytes per element as the fp32 tensor it replaces (two fp16 pieces), bit-identical operands -- and, in the
+    // single-piece modes (bf16 / f16: 2 bytes per element), each pair's output is written as a plane beside the
+    // fp32 residual, so that the next pair's first conv converts nothing either.
+    bool planes = v->planes && !v->dbg_absmax && c.resblock_type == 1;
+    for (int q = 0; q < v->per_rb() && planes; ++q) planes = plane_ok(v->rb[base + q].get());
+    const bool dual = planes && v->scheme != PARROT_PREC_F16X3;  // (one piece: the two planes share mid's 4 C T bytes per row)
+    char* const plane_a = reinterpret_cast<char*>(br.mid);
+    char* const plane_b = plane_a + (size_t)B * plane_row_bytes(v->scheme, v->chan(stage), T);
+    auto slope_of = [&](int q) { return v->rb[base + q]->d.pre_act == PRE_LRELU ? v->rb[base + q]->d.pre_slope : 1.f; };
+    const void* xin = nullptr;  // plane of `r` for the next first conv (dual mode)
+    const float* r = br.x;
+    for (int m = 0; m < nd; ++m) {
+        const bool last = (m == nd - 1);
+        float* dst = last ? br.y : ((m & 1) ? br.res_b : br.res_a);
+        if (m > 0) TRY(voc_amax(v, 1 + stage, r, n_act, br.s));
+        if (c.resblock_type == 1) {
+            o.planes = PlaneArgs();
+            o.planes.xplane = xin;
+            if (planes) { o.planes.yplane = plane_a; o.planes.plane_only = 1; o.planes.yslope = slope_of(2 * m + 1); }
+            TRY(conv_launch(v->rb[base + 2 * m].get(), r, nullptr, br.mid, B, T, EPI_STORE, 1.f, br.s, o));
+            TRY(voc_amax(v, 1 + stage, br.mid, n_act, br.s));
+        }
+        if (last && br.before_last) HIP_TRY(hipStreamWaitEvent(br.s, br.before_last, 0));
+        if (c.resblock_type == 1) {
+            o.planes = PlaneArgs();
+            if (planes) o.planes.xplane = plane_a;
+            if (dual && !last) { o.planes.yplane = plane_b; o.planes.yslope = slope_of(2 * m + 2); xin = plane_b; }
+            TRY(conv_launch(v->rb[base + 2 * m + 1].get(), br.mid, r, dst, B, T, last ? br.epi : EPI_STORE, br.div, br.s, o));
+        } else
+            TRY(conv_launch(v->rb[base + m].get(), r, r, dst, B, T, last ? br.epi : EPI_STORE, br.div, br.s, o));
+        r = dst;
+    }
+    return PARROT_OK;
+}
+
+// The MRF of a stage, y = sum_j ResBlock_j(x) / n_kernels, is one of four things:
+//   the whole stage in ONE launch (mrf_split_launch) when mrf_whole() says so; else per branch j, on its own stream when ns > 1,
+//   the split pair kernel (resblock_split_launch) | the fused exact kernel (resblock_fused_launch) | layer by layer.
+// Which kernel family runs a block never depends on the batch size or on the launch size: row b of a batch must equal the same
+// utterance run alone BIT FOR BIT -- the batched driver's byte-identical WAVs rest on it.  (At B = 1 the 96-column windows of the
+// 128- / 256-channel pair kernels are only 16-61 workgroups: 3.4 instead of 3.2 ms per utterance.)  The one exception is the whole-MRF
+// launch, which has the same bits as the per-branch pair kernels at 32 channels.
+// (the fused kernels address a batch row with 32-bit byte offsets: rows of 2 GiB and more go layer by layer)
+static bool row_fits_32bit(const parrot_voc* v, int stage, int T) { return (double)v->chan(stage) * T * 4.0 < 2147483648.0; }
+// every branch of the stage in ONE launch -- when that launch fills the chip twice over (one 512-thread workgroup per CU
+// walks 18 convs: a few windows are faster as per-branch launches on the branch streams; same bits either way at 32 channels)
+static bool mrf_whole(const parrot_voc* v, int stage, int B, int T) {
+    return v->mrf_ok[stage] && row_fits_32bit(v, stage, T) && (long)B * ((T + mrf_tile_cols(v, stage) - 1) / mrf_tile_cols(v, stage)) >= 2L * g_num_cus;
+}
+static int branch_launch(const parrot_voc* v, int stage, int j, const Branch& br) {
+    if (v->fused != 0 && v->branch_stream(stage, j) && row_fits_32bit(v, stage, br.T)) return resblock_split_launch(v, stage, j, br);
+    if (resblock_fusable(v, stage, j)) return resblock_fused_launch(v, stage, j, br);
+    return resblock_layers_launch(v, stage, j, br);
+}
+
+// ns_sized > 0 (chunked path): the number of concurrent MRF branches the caller sized the workspace with
 static int voc_forward_impl(parrot_voc_t* v, const int64_t* code, int code_stride, const int64_t* spkr, const float* feats,
                             int32_t n_feat_channels, const int32_t* unit_lens, int32_t B, int32_t U, float* wav_out,
-                            float* const* stage_out, void* ws, size_t ws_bytes, void* stream, int ns_sized, int lane) {
+                            float* const* stage_out, void* ws, size_t ws_bytes, void* stream, int ns_sized) {
     if (!v || !code || !wav_out || !ws) return fail(PARROT_E_INVALID, "voc_forward: null argument");
     {
         const int base = v->cfg.embedding_dim * (v->cfg.multispkr ? 2 : 1);
@@ -1545,17 +1519,15 @@ static int voc_forward_impl(parrot_voc_t* v, const int64_t* code, int code_strid
     float* x0 = a.take<float>((size_t)B * c.model_in_dim * U);
     const size_t mx = voc_max_act(v, B, U);
     // concurrent MRF branches: the shape's own rule, or -- chunked path -- the count the caller sized the workspace with
+    // (parrot_voc_workspace_bytes reserves exactly these; chunk lanes run without branch streams)
     const int ns = ns_sized > 0 ? std::min(ns_sized, v->mrf_streams) : voc_streams(v, B, U);
-    const int ns_alloc = ns;  // (parrot_voc_workspace_bytes reserves exactly these)
-    // (chunk lanes run without branch streams: `lane` only documents the caller)
-    (void)lane;
-    const parrot_voc::StreamSet& ss = v->ss[0];
+    const parrot_voc::StreamSet& ss = v->ss;
     std::unique_lock<std::mutex> side_lock(v->side_mu, std::defer_lock);
     if (ns > 1) side_lock.lock();
     float* P[3];
     for (int i = 0; i < 3; ++i) P[i] = a.take<float>(mx);
     float* TMP[PARROT_MAX_KERNELS][3];  // (T1, RA, RB) per concurrent branch
-    for (int j = 0; j < ns_alloc; ++j)
+    for (int j = 0; j < ns; ++j)
         for (int q = 0; q < 3; ++q) TMP[j][q] = a.take<float>(mx);
     if (!a.ok) return fail(PARROT_E_NOMEM, "voc_forward: workspace too small");
 
@@ -1574,112 +1546,60 @@ static int voc_forward_impl(parrot_voc_t* v, const int64_t* code, int code_strid
         if (stage_out && stage_out[idx]) HIP_TRY(hipMemcpyAsync(stage_out[idx], src, n * sizeof(float), hipMemcpyDeviceToDevice, s));
         return PARROT_OK;
     };
-    auto amax = [&](int group, const float* src, size_t n, hipStream_t q) -> int {  // debug: max |conv input| per layer group
-        if (v->dbg_absmax) {
-            hipLaunchKernelGGL(absmax_kernel, dim3((unsigned)std::min<size_t>((n + 255) / 256, 2048)), dim3(256), 0, q, src, n, v->dbg_absmax + group);
-            HIP_TRY(hipGetLastError());
-        }
-        return PARROT_OK;
-    };
     int ia = 0;
     // unit_lens (optional): per-row number of real units; every layer then applies ITS zero padding at the row's own
     // end (row_len * samples-per-unit so far), so a padded batch row equals the reference's B=1 run of that utterance
-    int mul = 1, add = 0;  // a row of n units holds n * mul + add samples at the current layer
-    TRY(amax(0, x0, (size_t)B * c.model_in_dim * U, s));
-    TRY(conv_launch(v->conv_pre.get(), x0, nullptr, P[ia], B, U, EPI_STORE, 1.f, 0, 0, 0, s, unit_lens, mul, add));
+    ConvOpts o;
+    o.rows.len = unit_lens;  // a row of n units holds n * mul + add samples at the current layer
+    TRY(voc_amax(v, 0, x0, (size_t)B * c.model_in_dim * U, s));
+    TRY(conv_launch(v->conv_pre.get(), x0, nullptr, P[ia], B, U, EPI_STORE, 1.f, s, o));
     TRY(snap(0, P[ia], (size_t)B * c.upsample_initial_channel * U));
     int T = U;
-    const int nk = c.n_kernels, nd = c.n_dil;
-    const int per_rb = (c.resblock_type == 1 ? 2 : 1) * nd;
+    const int nk = c.n_kernels;
     for (int i = 0; i < c.n_stages; ++i) {
         float* A = P[ia];
         float* X = P[(ia + 1) % 3];
         float* XS = P[(ia + 2) % 3];
-        TRY(amax(1 + i, A, (size_t)B * (c.upsample_initial_channel >> i) * T, s));
-        TRY(conv_launch(v->ups[i].get(), A, nullptr, X, B, T, EPI_STORE, 1.f, 0, 0, 0, s, unit_lens, mul, add));
+        TRY(voc_amax(v, 1 + i, A, (size_t)B * (c.upsample_initial_channel >> i) * T, s));
+        TRY(conv_launch(v->ups[i].get(), A, nullptr, X, B, T, EPI_STORE, 1.f, s, o));
         T = v->ups[i]->out_len(T);
-        mul *= c.upsample_rates[i];
-        add = add * c.upsample_rates[i] + ((c.upsample_kernel_sizes[i] - c.upsample_rates[i]) & 1);  // out_len(n mul + add)
+        o.rows.mul *= c.upsample_rates[i];
+        o.rows.add = o.rows.add * c.upsample_rates[i] + ((c.upsample_kernel_sizes[i] - c.upsample_rates[i]) & 1);  // out_len(n mul + add)
         const size_t n_act = (size_t)B * v->chan(i) * T;
         if (v->ev_stage[i] && !v->capturing) HIP_TRY(hipEventRecord(v->ev_stage[i], s));
         TRY(snap(1 + 2 * i, X, n_act));
-        // every branch of the stage in ONE launch -- when that launch fills the chip twice over (one 512-thread workgroup per CU
-        // walks 18 convs: a few windows are faster as per-branch launches on the branch streams; same bits either way at 32 channels)
-        if (v->mrf_ok[i] && (double)v->chan(i) * T * 4.0 < 2147483648.0 &&
-            (long)B * ((T + mrf_tile_cols(v, i) - 1) / mrf_tile_cols(v, i)) >= 2L * g_num_cus) {
-            TRY(amax(1 + i, X, n_act, s));
-            TRY(mrf_split_launch(v, i, X, XS, B, T, s, unit_lens, mul, add));
-            TRY(snap(2 + 2 * i, XS, n_act));
-            ia = (ia + 2) % 3;
-            continue;
-        }
-        if (ns > 1) {  // fork: the side streams see the upsampled stage input
-            HIP_TRY(hipEventRecord(ss.ev_fork, s));
-            for (int j = 1; j < ns; ++j) HIP_TRY(hipStreamWaitEvent(ss.side[j], ss.ev_fork, 0));
-        }
-        for (int j = 0; j < nk; ++j) {
-            // the longest branch (largest kernel size = last) stays on the caller's stream
-            const int slot = (ns > 1) ? (j + 1) % nk : 0;
-            hipStream_t sj = (slot == 0) ? s : ss.side[slot];
-            float* T1 = TMP[slot][0];
-            float* RA = TMP[slot][1];
-            float* RB = TMP[slot][2];
-            hipEvent_t order = (ns > 1 && j > 0) ? ss.ev_last[j - 1] : nullptr;  // XS accumulates in branch order (models.py:100-106)
-            const float* r = X;
-            const int base = (i * nk + j) * per_rb;
-            const int epi_last = (nk == 1 || j == 0) ? EPI_STORE : (j == nk - 1 ? EPI_ADD_DIV : EPI_ADD);
-            // (the fused kernels address a batch row with 32-bit byte offsets: rows of 2 GiB and more go layer by layer)
-            // (which kernel family runs a block never depends on the batch size or on the launch size: row b of a batch must equal
-            //  the same utterance run alone BIT FOR BIT -- the batched driver's byte-identical WAVs rest on it.  At B = 1 the
-            //  96-column windows of the 128- / 256-channel pair kernels are only 16-61 workgroups: 3.4 instead of 3.2 ms per utterance)
-            if (j == 0) TRY(amax(1 + i, X, n_act, s));  // the stage input feeds the first conv of every branch
-            if (v->fused != 0 && v->rb_stream[(size_t)i * nk + j] && (double)v->chan(i) * T * 4.0 < 2147483648.0) {
-                TRY(resblock_split_launch(v, i, j, X, XS, RA, RB, B, T, epi_last, (float)nk, sj, unit_lens, mul, add, order));
-            } else if (resblock_fusable(v, i, j)) {
-                TRY(resblock_fused_launch(v, i, j, X, XS, B, T, epi_last, (float)nk, sj, unit_lens, mul, add, order));
-            } else {
-                // Operand planes (conv_split16.h; PARROT_PLANES=0 switches them off): the tensor between the two convs of a pair
-                // exists only as the second conv's ready-made operand -- written once by the first conv's epilogue, the same
-                // bytes per element as the fp32 tensor it replaces (two fp16 pieces), bit-identical operands -- and, in the
-                // single-piece modes (bf16 / f16: 2 bytes per element), each pair's output is written as a plane beside the
-                // fp32 residual, so that the next pair's first conv converts nothing either.
-                bool planes = v->planes && !v->dbg_absmax && c.resblock_type == 1;
-                for (int q = 0; q < per_rb && planes; ++q) planes = plane_ok(v->rb[base + q].get());
-                const bool dual = planes && v->scheme != PARROT_PREC_F16X3;  // (one piece: the two planes share T1's 4 C T bytes per row)
-                char* const plane_a = reinterpret_cast<char*>(T1);
-                char* const plane_b = plane_a + (size_t)B * plane_row_bytes(v->scheme, v->chan(i), T);
-                const void* xin = nullptr;  // plane of `r` for the next first conv (dual mode)
-                for (int m = 0; m < nd; ++m) {
-                    const bool last = (m == nd - 1);
-                    float* dst = last ? XS : ((m & 1) ? RB : RA);
-                    if (m > 0) TRY(amax(1 + i, r, n_act, sj));
-                    if (c.resblock_type == 1) {
-                        PlaneArgs pa;
-                        pa.xplane = xin;
-                        if (planes) { pa.yplane = plane_a; pa.plane_only = 1; pa.yslope = v->rb[base + 2 * m + 1]->d.pre_act == PRE_LRELU ? v->rb[base + 2 * m + 1]->d.pre_slope : 1.f; }
-                        TRY(conv_launch(v->rb[base + 2 * m].get(), r, nullptr, T1, B, T, EPI_STORE, 1.f, 0, 0, 0, sj, unit_lens, mul, add, planes ? &pa : nullptr));
-                        TRY(amax(1 + i, T1, n_act, sj));
-                    }
-                    if (last && order) HIP_TRY(hipStreamWaitEvent(sj, order, 0));
-                    if (c.resblock_type == 1) {
-                        PlaneArgs pa;
-                        if (planes) pa.xplane = plane_a;
-                        if (dual && !last) { pa.yplane = plane_b; pa.yslope = v->rb[base + 2 * m + 2]->d.pre_act == PRE_LRELU ? v->rb[base + 2 * m + 2]->d.pre_slope : 1.f; xin = plane_b; }
-                        TRY(conv_launch(v->rb[base + 2 * m + 1].get(), T1, r, dst, B, T, last ? epi_last : EPI_STORE, (float)nk, 0, 0, 0, sj, unit_lens, mul, add, planes ? &pa : nullptr));
-                    } else
-                        TRY(conv_launch(v->rb[base + m].get(), r, r, dst, B, T, last ? epi_last : EPI_STORE, (float)nk, 0, 0, 0, sj, unit_lens, mul, add));
-                    r = dst;
-                }
+        if (mrf_whole(v, i, B, T)) {
+            TRY(voc_amax(v, 1 + i, X, n_act, s));
+            TRY(mrf_split_launch(v, i, X, XS, B, T, s, o.rows));
+        } else {
+            if (ns > 1) {  // fork: the side streams see the upsampled stage input
+                HIP_TRY(hipEventRecord(ss.ev_fork, s));
+                for (int j = 1; j < ns; ++j) HIP_TRY(hipStreamWaitEvent(ss.side[j], ss.ev_fork, 0));
             }
-            if (ns > 1) HIP_TRY(hipEventRecord(ss.ev_last[j], sj));
+            for (int j = 0; j < nk; ++j) {
+                // the longest branch (largest kernel size = last) stays on the caller's stream
+                const int slot = (ns > 1) ? (j + 1) % nk : 0;
+                if (j == 0) TRY(voc_amax(v, 1 + i, X, n_act, s));  // the stage input feeds the first conv of every branch
+                Branch br{};
+                br.x = X; br.y = XS;
+                br.mid = TMP[slot][0]; br.res_a = TMP[slot][1]; br.res_b = TMP[slot][2];
+                br.B = B; br.T = T;
+                br.epi = (nk == 1 || j == 0) ? EPI_STORE : (j == nk - 1 ? EPI_ADD_DIV : EPI_ADD);
+                br.div = (float)nk;
+                br.s = (slot == 0) ? s : ss.side[slot];
+                br.rows = o.rows;
+                br.before_last = (ns > 1 && j > 0) ? ss.ev_last[j - 1] : nullptr;  // XS accumulates in branch order (models.py:100-106)
+                TRY(branch_launch(v, i, j, br));
+                if (ns > 1) HIP_TRY(hipEventRecord(ss.ev_last[j], br.s));
+            }
+            if (ns > 1)  // join: every branch (and with it every reader of X and of the branch temporaries) is done
+                for (int j = 0; j < nk; ++j) HIP_TRY(hipStreamWaitEvent(s, ss.ev_last[j], 0));
         }
-        if (ns > 1)  // join: every branch (and with it every reader of X and of the branch temporaries) is done
-            for (int j = 0; j < nk; ++j) HIP_TRY(hipStreamWaitEvent(s, ss.ev_last[j], 0));
         TRY(snap(2 + 2 * i, XS, n_act));
         ia = (ia + 2) % 3;
     }
-    TRY(amax(1 + c.n_stages, P[ia], (size_t)B * v->chan(c.n_stages - 1) * T, s));
-    TRY(conv_launch(v->conv_post.get(), P[ia], nullptr, wav_out, B, T, EPI_STORE, 1.f, 0, 0, 0, s, unit_lens, mul, add));
+    TRY(voc_amax(v, 1 + c.n_stages, P[ia], (size_t)B * v->chan(c.n_stages - 1) * T, s));
+    TRY(conv_launch(v->conv_post.get(), P[ia], nullptr, wav_out, B, T, EPI_STORE, 1.f, s, o));
     return PARROT_OK;
 }
 
@@ -1812,21 +1732,8 @@ static int build_fft(std::unique_ptr<FftLayer>& slot, const parrot_tte_cfg& c, i
     return PARROT_OK;
 }
 
-static int tte_create_body(parrot_tte_t** out, const parrot_tte_cfg* cfg, const parrot_tte_weights* w);
-static int tte_create_impl(parrot_tte_t** out, const parrot_tte_cfg* cfg, const parrot_tte_weights* w, int prec, int merge) {
+static int tte_create(parrot_tte_t** out, const parrot_tte_cfg* cfg, const parrot_tte_weights* w, int prec, int merge) {
     CreateScope scope(prec, -1, merge);  // (thread-local: the process defaults are not touched)
-    return tte_create_body(out, cfg, w);
-}
-extern "C" int parrot_tte_create(parrot_tte_t** out, const parrot_tte_cfg* cfg, const parrot_tte_weights* w) {
-    return tte_create_impl(out, cfg, w, -1, -1);
-}
-extern "C" int parrot_tte_create_ex(parrot_tte_t** out, const parrot_tte_cfg* cfg, const parrot_tte_weights* w, int32_t precision,
-                                    int32_t merge_projections) {
-    if (precision > PARROT_PREC_F16 || merge_projections > 1) return fail(PARROT_E_INVALID, "tte_create_ex: precision in -1 .. 4, merge_projections in -1 .. 1");
-    return tte_create_impl(out, cfg, w, precision, merge_projections);
-}
-extern "C" int parrot_tte_precision(const parrot_tte_t* t) { return t ? t->scheme : PARROT_E_INVALID; }
-static int tte_create_body(parrot_tte_t** out, const parrot_tte_cfg* cfg, const parrot_tte_weights* w) {
     if (!out || !cfg || !w) return fail(PARROT_E_INVALID, "tte_create: null argument");
     const parrot_tte_cfg& c = *cfg;
     if (c.d_model <= 0 || c.n_filter_ffn <= 0 || c.max_len <= 0 || c.vocab <= 0 || c.n_codes <= 0 || c.dp_filter <= 0 ||
@@ -1895,6 +1802,13 @@ static int tte_create_body(parrot_tte_t** out, const parrot_tte_cfg* cfg, const 
     *out = t.release();
     return PARROT_OK;
 }
+extern "C" int parrot_tte_create(parrot_tte_t** out, const parrot_tte_cfg* cfg, const parrot_tte_weights* w) { return tte_create(out, cfg, w, -1, -1); }
+extern "C" int parrot_tte_create_ex(parrot_tte_t** out, const parrot_tte_cfg* cfg, const parrot_tte_weights* w, int32_t precision,
+                                    int32_t merge_projections) {
+    if (precision > PARROT_PREC_F16 || merge_projections > 1) return fail(PARROT_E_INVALID, "tte_create_ex: precision in -1 .. 4, merge_projections in -1 .. 1");
+    return tte_create(out, cfg, w, precision, merge_projections);
+}
+extern "C" int parrot_tte_precision(const parrot_tte_t* t) { return t ? t->scheme : PARROT_E_INVALID; }
 extern "C" void parrot_tte_destroy(parrot_tte_t* t) { delete t; }
 
 struct TteState {  // persists between encode and decode (sized by B,S only)
@@ -1944,6 +1858,12 @@ extern "C" size_t parrot_tte_workspace_bytes(const parrot_tte_t* t, int32_t B, i
     return align_up(a.off, 256);
 }
 
+// row-exact mode: row b holds len[b] real positions (NULL: dense rows)
+static ConvOpts rows_of(const int32_t* len) {
+    ConvOpts o;
+    o.rows.len = len;
+    return o;
+}
 static int layernorm(const float* x, const float* g, const float* b, float* y, int B, int C, int T, int relu_in, hipStream_t s) {
     hipLaunchKernelGGL(layernorm_cf_kernel<16>, dim3((T + 63) / 64, B), dim3(16 * 64), 0, s, x, g, b, y, C, T, 1e-5f, relu_in);
     HIP_TRY(hipGetLastError());
@@ -1959,10 +1879,10 @@ static int fft_block(const parrot_tte* t, const FftLayer* L, TteScratch& w, floa
     const int D = t->cfg.d_model, H = L->heads, hd = D / H;
     TRY(layernorm(x, L->an_w, L->an_b, w.n, B, D, T, 0, s));
     if (L->merged) {
-        TRY(conv_launch(L->qkv.get(), w.n, nullptr, w.qkv2, B, T, EPI_STORE, 1.f, 0, 0, 0, s));
+        TRY(conv_launch(L->qkv.get(), w.n, nullptr, w.qkv2, B, T, EPI_STORE, 1.f, s));
     } else {
-        TRY(conv_launch(L->qkv.get(), w.n, nullptr, w.qkv1, B, T, EPI_STORE, 1.f, 0, 0, 0, s));
-        TRY(conv_launch(L->in_proj.get(), w.qkv1, nullptr, w.qkv2, B, T, EPI_STORE, 1.f, 0, 0, 0, s));
+        TRY(conv_launch(L->qkv.get(), w.n, nullptr, w.qkv1, B, T, EPI_STORE, 1.f, s));
+        TRY(conv_launch(L->in_proj.get(), w.qkv1, nullptr, w.qkv2, B, T, EPI_STORE, 1.f, s));
     }
     const long DT = (long)D * T;
     if (t->flash) {  // any T, online softmax, no score tensor (attn.h: attn_flash_kernel)
@@ -2006,15 +1926,15 @@ static int fft_block(const parrot_tte* t, const FftLayer* L, TteScratch& w, floa
     }
     }
     if (L->merged) {
-        TRY(conv_launch(L->wo.get(), w.ctx, x, w.h, B, T, EPI_STORE, 1.f, 0, 0, 0, s));        // h = x + attn
+        TRY(conv_launch(L->wo.get(), w.ctx, x, w.h, B, T, EPI_STORE, 1.f, s));        // h = x + attn
     } else {
-        TRY(conv_launch(L->out_proj.get(), w.ctx, nullptr, w.o, B, T, EPI_STORE, 1.f, 0, 0, 0, s));
-        TRY(conv_launch(L->wo.get(), w.o, x, w.h, B, T, EPI_STORE, 1.f, 0, 0, 0, s));          // h = x + attn
+        TRY(conv_launch(L->out_proj.get(), w.ctx, nullptr, w.o, B, T, EPI_STORE, 1.f, s));
+        TRY(conv_launch(L->wo.get(), w.o, x, w.h, B, T, EPI_STORE, 1.f, s));          // h = x + attn
     }
     TRY(layernorm(w.h, L->cn_w, L->cn_b, w.n, B, D, T, 0, s));
     // (a 1x1 conv has no neighbours to leak from: only the k > 1 convs take the per-row ends)
-    TRY(conv_launch(L->conv1.get(), w.n, nullptr, w.f, B, T, EPI_STORE, 1.f, 0, 0, 0, s, t->cfg.ffn_k1 > 1 ? row_len : nullptr));  // relu fused
-    TRY(conv_launch(L->conv2.get(), w.f, w.h, x, B, T, EPI_STORE, 1.f, 0, 0, 0, s, t->cfg.ffn_k2 > 1 ? row_len : nullptr));      // out = h + ffn
+    TRY(conv_launch(L->conv1.get(), w.n, nullptr, w.f, B, T, EPI_STORE, 1.f, s, rows_of(t->cfg.ffn_k1 > 1 ? row_len : nullptr)));  // relu fused
+    TRY(conv_launch(L->conv2.get(), w.f, w.h, x, B, T, EPI_STORE, 1.f, s, rows_of(t->cfg.ffn_k2 > 1 ? row_len : nullptr)));      // out = h + ffn
     return PARROT_OK;
 }
 
@@ -2063,11 +1983,11 @@ static int tte_encode_rows(parrot_tte_t* t, const int64_t* phones, const uint8_t
     HIP_TRY(hipMemcpyAsync(st.enc_out, w.x, (size_t)B * D * S * sizeof(float), hipMemcpyDeviceToDevice, s));
     // duration predictor (duration.py:29-48): conv -> relu -> LN -> conv(pad 1) -> relu -> LN -> linear
     const int NF = c.dp_filter;
-    TRY(conv_launch(t->dp0.get(), w.x, nullptr, w.f, B, S, EPI_STORE, 1.f, 0, 0, 0, s, src_len));
+    TRY(conv_launch(t->dp0.get(), w.x, nullptr, w.f, B, S, EPI_STORE, 1.f, s, rows_of(src_len)));
     TRY(layernorm(w.f, t->ln0_w, t->ln0_b, w.n, B, NF, S, 1, s));
-    TRY(conv_launch(t->dp1.get(), w.n, nullptr, w.f, B, S, EPI_STORE, 1.f, 0, 0, 0, s, src_len));
+    TRY(conv_launch(t->dp1.get(), w.n, nullptr, w.f, B, S, EPI_STORE, 1.f, s, rows_of(src_len)));
     TRY(layernorm(w.f, t->ln1_w, t->ln1_b, w.n, B, NF, S, 1, s));
-    TRY(conv_launch(t->dp_proj.get(), w.n, nullptr, w.o, B, S, EPI_STORE, 1.f, 0, 0, 0, s));  // (B,1,S)
+    TRY(conv_launch(t->dp_proj.get(), w.n, nullptr, w.o, B, S, EPI_STORE, 1.f, s));  // (B,1,S)
     hipLaunchKernelGGL(duration_kernel, dim3(B), dim3(256), 0, s, w.o, src_mask, log_dur, dur, st.cum, st.out_len, S, src_len);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(out_lens, st.out_len, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
@@ -2129,7 +2049,7 @@ static int tte_decode_rows(parrot_tte_t* t, int32_t Bfull, int32_t S, int32_t L,
         TRY(fft_block(t, t->dec[n].get(), w, w.x, valid, B, L, s, row_exact ? st.out_len + row0 : nullptr));
         TRY(dbg(1 + n, w.x, (size_t)B * D * L));
     }
-    TRY(conv_launch(t->head.get(), w.x, nullptr, w.logits, B, L, EPI_STORE, 1.f, 0, 0, 0, s));
+    TRY(conv_launch(t->head.get(), w.x, nullptr, w.logits, B, L, EPI_STORE, 1.f, s));
     {   // argmax + tie guard: gstat = {count, ids changed, min margin (float bits)} of this decode
         const bool on = t->guard > 0.f;  // (length_regulate_kernel, the first kernel of this decode, has reset gstat)
         hipLaunchKernelGGL(argmax_cf_kernel, dim3((L + 63) / 64, B), dim3(64 * ARGMAX_WAVES), 0, s, w.logits, ids, V, L, t->err, t->guard,

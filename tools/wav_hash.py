@@ -1,9 +1,13 @@
 #!/usr/bin/env python3
 """SHA-256 of the vocoder output for a few launch shapes (dense and ragged batches): two builds / switch settings that claim the
-same arithmetic must print the same lines.   PARROT_PLANES=0 python tools/wav_hash.py ; PARROT_PLANES=1 python tools/wav_hash.py"""
+same arithmetic must print the same lines.   PARROT_PLANES=0 python tools/wav_hash.py ; PARROT_PLANES=1 python tools/wav_hash.py
+--tte: the same for the TTE -- the ids, target mask, durations and log-durations of the full-size synthetic model's inference at
+B = 64 x S = 64 (dense and ragged) and at B = 1."""
 import hashlib
+import json
 import os
 import sys
+import tempfile
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
@@ -12,7 +16,33 @@ from parrot_tts_amd import synth  # noqa: E402
 from parrot_tts_amd.vocoder import AttrDict, CodeGenerator  # noqa: E402
 
 
+def tte_main():
+    from parrot_tts_amd.tte import Parrot
+    cfg, vocab, n_spk = synth.default_tte_config(), 300, 10
+    with tempfile.TemporaryDirectory() as tmp:  # (the speaker table is read at construction)
+        cfg["path"]["root_path"] = tmp
+        with open(os.path.join(tmp, "speakers.json"), "w") as f:
+            json.dump({f"spk{i}": i for i in range(n_spk)}, f)
+        m = Parrot(cfg, vocab, 0)
+    m.load_state_dict(synth.synth_tte_state_dict(cfg, vocab, n_spk, seed=42, forced_duration=4))
+    m = m.eval().to("cuda:0")
+    for B, S, ragged in [(64, 64, False), (64, 64, True), (1, 64, False)]:
+        batch = {k: v.to("cuda:0") for k, v in synth.synth_tte_batch(B, S, vocab, n_spk, seed=B + S, ragged=ragged).items()}
+        for row_exact in (False, True):
+            with torch.no_grad():
+                r = m.infer_dense(batch, row_exact=row_exact)
+            m.check_outputs()
+            # (ids past a row's end and durations at padded source positions are unspecified)
+            src, tgt = batch["src_mask"].bool(), r["tgt_mask"].bool()
+            out = {"ids": r["ids"].masked_fill(~tgt, 0), "tgt_mask": r["tgt_mask"], "dur": r["dur"].masked_fill(~src, 0),
+                   "log_dur": r["log_dur"].masked_fill(~src, 0)}
+            hs = [hashlib.sha256(out[k].cpu().numpy().tobytes()).hexdigest()[:16] for k in ("ids", "tgt_mask", "dur", "log_dur")]
+            print("tte", B, S, "ragged" if ragged else "dense", "row_exact" if row_exact else "padded", *hs, flush=True)
+
+
 def main():
+    if "--tte" in sys.argv:
+        return tte_main()
     h = synth.default_voc_config()
     g = CodeGenerator(AttrDict(h))
     g.load_state_dict(synth.synth_voc_state_dict(h, seed=1234, scale=1.0))
