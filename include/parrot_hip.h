@@ -314,6 +314,57 @@ size_t parrot_length_regulator_workspace_bytes(int32_t B, int32_t S, int32_t D, 
 int parrot_length_regulator(const float* seq, const int64_t* dur, int32_t B, int32_t S, int32_t D, int32_t L, float* out,
                             uint8_t* mask, int32_t* out_lens, void* ws, size_t ws_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Log-mel spectrogram and mel L1: the vocoder's validation metric (validation/mel_spec_error, utils/vocoder/train.py:198-227):
+ * mel_spectrogram (utils/vocoder/dataset.py:43-69, center = False) and F.l1_loss of two such spectrograms (train.py:213).
+ *   reflect-pad by (n_fft - hop) / 2 -> STFT with the caller's fp32 window (zero-padded, centred, to n_fft as torch.stft does)
+ *   -> sqrt(re^2 + im^2 + 1e-9) -> basis @ spec -> log(clamp(., 1e-5)).
+ * The framed DFT runs as a Conv1d (hop -> 2 (n_fft / 2 + 1) channels, ceil(n_fft / hop) taps) over a polyphase view of the padded
+ * signal and the mel projection as a 1x1 conv, both on the parrot_conv kernels; their weights are formed in fp64 from the fp32
+ * window and rounded once.  window_host[win] and basis_host[n_mels x (n_fft / 2 + 1)] (row-major) are HOST data of the caller:
+ * the library never computes a window or a mel scale.
+ * Precision: the parity-grade modes only -- PARROT_PREC_F16X3 (default), PARROT_PREC_BF16X6, PARROT_PREC_F32.  Under a process
+ * default of PARROT_PREC_BF16 / PARROT_PREC_F16 a mel handle is built in PARROT_PREC_F16X3: the metric does not move with the
+ * vocoder's operating point (asking parrot_mel_create_ex for one of the two is PARROT_E_UNSUPPORTED).  The fp16x3 range rule
+ * applies to the spectral magnitudes (< 8190: a full-scale sine at n_fft = 1024 reaches 512).  PARROT_PREC_F32 sums the DFT in
+ * up to 8 channel groups whose partial sums are added afterwards (one fp32 accumulator chain over n_fft products costs more
+ * accuracy than the split schemes lose), each group with its own 2 (n_fft / 2 + 1) rows padded to whole 128-row tiles: its
+ * spectrum workspace is up to 9 times that of the other two modes (n_fft 1024: 8 x 1152 rows against 1026).
+ * ------------------------------------------------------------------------------------------ */
+typedef struct parrot_mel parrot_mel_t;
+
+typedef struct {
+    int32_t n_fft, hop, win, n_mels; /* h.n_fft, h.hop_size, h.win_size, h.num_mels; 1 <= hop <= n_fft, win <= n_fft */
+} parrot_mel_cfg;
+
+int parrot_mel_create(parrot_mel_t** out, const parrot_mel_cfg* cfg, const float* window_host, const float* basis_host);
+int parrot_mel_create_ex(parrot_mel_t** out, const parrot_mel_cfg* cfg, const float* window_host, const float* basis_host,
+                         int32_t precision /* PARROT_PREC_F32 / BF16X6 / F16X3; -1 = default */);
+void parrot_mel_destroy(parrot_mel_t*);
+int parrot_mel_precision(const parrot_mel_t*);
+/* frames of a row of n_samples samples: n_samples / hop */
+int parrot_mel_frames(const parrot_mel_t*, int32_t n_samples);
+size_t parrot_mel_workspace_bytes(const parrot_mel_t*, int32_t B, int32_t N);
+/* wav: B rows of N fp32 samples, row_stride elements apart -> mel_out (B, n_mels, N / hop) fp32.
+ * n_samples: optional (B) int32 device array of real samples per row (ragged batch padded to N): the reflection happens at each
+ * row's own end, row b yields n_samples[b] / hop frames that equal that utterance run alone bit for bit, samples beyond
+ * n_samples[b] are never read, and the frames beyond are written as zero.  NULL = all N.
+ * Reported by parrot_mel_check / parrot_mel_status_async, not by the return value: status 8, a row no longer than the reflect
+ * pad (torch's F.pad raises); status 5, a non-finite mel value (NaN / inf input, or the fp16x3 range exceeded). */
+int parrot_mel_forward(parrot_mel_t*, const float* wav, int64_t row_stride, const int32_t* n_samples /* nullable */, int32_t B, int32_t N,
+                       float* mel_out, void* ws, size_t ws_bytes, void* stream);
+/* sum |a - b| per row over n_mels x n_frames[b] (NULL: T) elements of two (B, n_mels, T) fp32 device tensors.  fp64 sums in a
+ * fixed order, no value atomics: two calls agree bit for bit.  out_f64 (2B doubles) <- the row sums, then the row counts
+ * n_mels * n_frames[b]; mean_f32 (1 float, nullable) <- sum of sums / sum of counts, rounded once to fp32 (F.l1_loss's mean
+ * when the rows are of one length; NaN for an empty batch). */
+size_t parrot_mel_l1_workspace_bytes(int32_t B, int32_t n_mels, int32_t T);
+int parrot_mel_l1(const float* a, const float* b, const int32_t* n_frames /* nullable */, int32_t B, int32_t n_mels, int32_t T,
+                  double* out_f64, float* mean_f32 /* nullable */, void* ws, size_t ws_bytes, void* stream);
+/* Synchronises `stream`, clears the flag: 0, PARROT_E_INVALID (status 8) or PARROT_E_NONFINITE (status 5). */
+int parrot_mel_check(parrot_mel_t*, void* stream);
+/* The same flag without a synchronisation: see parrot_voc_status_async. */
+int parrot_mel_status_async(parrot_mel_t*, int32_t* dst_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -62,6 +62,10 @@ class TteWeights(C.Structure):
                 ("head_w", c_float_p), ("head_b", c_float_p)]
 
 
+class MelCfg(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("n_fft", "hop", "win", "n_mels")]
+
+
 # name -> (restype, argtypes); every symbol include/parrot_hip.h and include/parrot_hip_debug.h declare
 vp, i32, sz, f32 = C.c_void_p, C.c_int32, C.c_size_t, C.c_float
 SIGNATURES = {
@@ -118,6 +122,17 @@ SIGNATURES = {
     "parrot_tte_debug_stages": (C.c_int, [vp, C.POINTER(vp), C.POINTER(vp)]),
     "parrot_length_regulator_workspace_bytes": (sz, [i32, i32, i32, i32]),
     "parrot_length_regulator": (C.c_int, [vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, sz, vp]),
+    "parrot_mel_create": (C.c_int, [C.POINTER(vp), C.POINTER(MelCfg), c_float_p, c_float_p]),
+    "parrot_mel_create_ex": (C.c_int, [C.POINTER(vp), C.POINTER(MelCfg), c_float_p, c_float_p, i32]),
+    "parrot_mel_destroy": (None, [vp]),
+    "parrot_mel_precision": (C.c_int, [vp]),
+    "parrot_mel_frames": (C.c_int, [vp, i32]),
+    "parrot_mel_workspace_bytes": (sz, [vp, i32, i32]),
+    "parrot_mel_forward": (C.c_int, [vp, vp, C.c_int64, vp, i32, i32, vp, vp, sz, vp]),
+    "parrot_mel_l1_workspace_bytes": (sz, [i32, i32, i32]),
+    "parrot_mel_l1": (C.c_int, [vp, vp, vp, i32, i32, i32, vp, vp, vp, sz, vp]),
+    "parrot_mel_check": (C.c_int, [vp, vp]),
+    "parrot_mel_status_async": (C.c_int, [vp, vp, vp]),
 }
 
 _lib = None
