@@ -365,6 +365,74 @@ int parrot_mel_check(parrot_mel_t*, void* stream);
 /* The same flag without a synchronisation: see parrot_voc_status_async. */
 int parrot_mel_status_async(parrot_mel_t*, int32_t* dst_dev, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Forced aligner: Aligner.forward (utils/aligner/model.py:24-48), the softmax of utils/aligner/extract_durations.py:91-93 and
+ * extract_durations_with_dijkstra (utils/aligner/duration_extraction.py:52-85).
+ *   mel (B, T, n_mels) -> 3 x [Conv1d(k = 5, pad 2, no bias) -> ReLU -> BatchNorm1d (eval, running statistics)] (model.py:6-21)
+ *   -> one-layer bidirectional LSTM (gates i, f, g, o; output [forward, backward]) -> Linear(2 lstm_dim, num_symbols).
+ * The five GEMMs run on the parrot_conv kernels (the LSTM input projection of both directions for all frames as one 1x1 plan);
+ * the recurrence is one launch of lstm_step_kernel per frame, fp32 in every mode, with stream order as its only synchronisation.
+ * The padded batch runs as it stands (dataset.py:66-75): the backward direction of a short row starts inside the padding, so a
+ * row's logits depend on the T it is padded to, as the reference's do; mel_len enters at the softmax.
+ * conv_dim and lstm_dim: multiples of 16 (else PARROT_E_UNSUPPORTED), lstm_dim <= 1024; n_mels, num_symbols, B arbitrary;
+ * T <= 32768 frames, N <= 2048 tokens per utterance (beyond: PARROT_E_UNSUPPORTED).
+ * Precision: as the mel handle -- PARROT_PREC_F16X3 (default), PARROT_PREC_BF16X6, PARROT_PREC_F32; under a process default of
+ * PARROT_PREC_BF16 / PARROT_PREC_F16 the handle is built in PARROT_PREC_F16X3 and asking _create_ex for either is
+ * PARROT_E_UNSUPPORTED.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct parrot_aligner parrot_aligner_t;
+
+typedef struct {
+    int32_t n_mels, num_symbols, lstm_dim, conv_dim; /* Aligner.__init__ (model.py:26-30); num_symbols = len(symbols) + 1 */
+    float bn_eps;                                    /* BatchNorm1d.eps (1e-5) */
+} parrot_aligner_cfg;
+
+/* fp32 HOST pointers, torch layouts (state_dict keys of model.py in brackets) */
+typedef struct {
+    const float* conv_w[3];    /* [convs.i.conv.weight]  (conv_dim, n_mels | conv_dim, 5) */
+    const float* bn_weight[3]; /* [convs.i.bnorm.weight / bias / running_mean / running_var]  (conv_dim) each */
+    const float* bn_bias[3];
+    const float* bn_mean[3];
+    const float* bn_var[3];
+    const float* w_ih[2];      /* [rnn.weight_ih_l0, rnn.weight_ih_l0_reverse]  (4 lstm_dim, conv_dim) */
+    const float* w_hh[2];      /* [rnn.weight_hh_l0, ..._reverse]               (4 lstm_dim, lstm_dim) */
+    const float* b_ih[2];      /* [rnn.bias_ih_l0, ..._reverse]                 (4 lstm_dim) */
+    const float* b_hh[2];      /* [rnn.bias_hh_l0, ..._reverse]                 (4 lstm_dim) */
+    const float* lin_w;        /* [lin.weight]  (num_symbols, 2 lstm_dim) */
+    const float* lin_b;        /* [lin.bias]    (num_symbols) */
+} parrot_aligner_weights;
+
+int parrot_aligner_create(parrot_aligner_t** out, const parrot_aligner_cfg* cfg, const parrot_aligner_weights* w);
+int parrot_aligner_create_ex(parrot_aligner_t** out, const parrot_aligner_cfg* cfg, const parrot_aligner_weights* w,
+                             int32_t precision /* PARROT_PREC_F32 / BF16X6 / F16X3; -1 = default */);
+void parrot_aligner_destroy(parrot_aligner_t*);
+int parrot_aligner_precision(const parrot_aligner_t*);
+size_t parrot_aligner_workspace_bytes(const parrot_aligner_t*, int32_t B, int32_t T);
+/* Aligner.forward (model.py:41-48): mel (B, T, n_mels) fp32 -> logits (B, T, num_symbols) fp32, every frame of the padded batch. */
+int parrot_aligner_forward(parrot_aligner_t*, const float* mel, int32_t B, int32_t T, float* logits, void* ws, size_t ws_bytes, void* stream);
+/* torch.softmax(logits[b, :mel_len[b]], -1) (extract_durations.py:91-93): logits (B, T, num_symbols) -> pred of the same shape,
+ * fp32, max-shifted; mel_len (B) int32 device (NULL: T); frames at or beyond mel_len[b] are written as zero.  May run in place.
+ * A non-finite logit of a real frame sets status 5, a mel_len[b] outside [1, T] status 9 (it is clamped, nothing is read through
+ * it; 9 wins over 5) (parrot_aligner_check / _status_async). */
+int parrot_align_softmax(parrot_aligner_t*, const float* logits, const int32_t* mel_len, int32_t B, int32_t T, float* pred, void* stream);
+/* Synchronises `stream`, clears the flag: 0, PARROT_E_NONFINITE (status 5) or PARROT_E_INVALID (status 9). */
+int parrot_aligner_check(parrot_aligner_t*, void* stream);
+/* The same flag without a synchronisation: see parrot_voc_status_async. */
+int parrot_aligner_status_async(parrot_aligner_t*, int32_t* dst_dev, void* stream);
+/* extract_durations_with_dijkstra (duration_extraction.py:52-85) for a ragged batch, one workgroup per utterance.  It takes
+ * PROBABILITIES: pred (B, T, V) fp32, tokens (B, N) int64, mel_len / tokens_len (B) int32, all device; row b uses
+ * pred[b, :mel_len[b]] and tokens[b, :tokens_len[b]] (tokens_len[b] > mel_len[b] is legal).
+ *   w[i][j] = fl32(1 - pred[i][tokens[j]]) widened to fp64; dist[0][0] = 0,
+ *   dist[i][j] = min(dist[i-1][j-1], dist[i-1][j], dist[i][j-1]) + w[i][j] in fp64 -- the sums scipy's Dijkstra forms;
+ * every frame counts for the last token the cheapest path visits in its row.  Tie rule (the reference's choice among equally
+ * cheap paths follows no fixed rule): equal predecessors -> diagonal, then previous frame, then previous token.
+ * dur_out (B, N) int32 (sums to mel_len[b]; zero beyond tokens_len[b]), cost_out (B) fp64 = dist[mel_len-1][tokens_len-1].
+ * ws: parrot_align_workspace_bytes(B, T, N); its first int32 is the call's status, 0 or 9: a token outside [0, V) or a length
+ * outside [1, T] / [1, N] -- nothing is read through such a value; that row's durations are zero and its cost NaN. */
+size_t parrot_align_workspace_bytes(int32_t B, int32_t T, int32_t N);
+int parrot_align_durations(const float* pred, const int64_t* tokens, const int32_t* mel_len, const int32_t* tokens_len, int32_t B, int32_t T,
+                           int32_t V, int32_t N, int32_t* dur_out, double* cost_out, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

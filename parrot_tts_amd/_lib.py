@@ -66,6 +66,15 @@ class MelCfg(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("n_fft", "hop", "win", "n_mels")]
 
 
+class AlignerCfg(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("n_mels", "num_symbols", "lstm_dim", "conv_dim")] + [("bn_eps", C.c_float)]
+
+
+class AlignerWeights(C.Structure):
+    _fields_ = [(n, c_float_p * 3) for n in ("conv_w", "bn_weight", "bn_bias", "bn_mean", "bn_var")] + \
+               [(n, c_float_p * 2) for n in ("w_ih", "w_hh", "b_ih", "b_hh")] + [("lin_w", c_float_p), ("lin_b", c_float_p)]
+
+
 # name -> (restype, argtypes); every symbol include/parrot_hip.h and include/parrot_hip_debug.h declare
 vp, i32, sz, f32 = C.c_void_p, C.c_int32, C.c_size_t, C.c_float
 SIGNATURES = {
@@ -133,6 +142,18 @@ SIGNATURES = {
     "parrot_mel_l1": (C.c_int, [vp, vp, vp, i32, i32, i32, vp, vp, vp, sz, vp]),
     "parrot_mel_check": (C.c_int, [vp, vp]),
     "parrot_mel_status_async": (C.c_int, [vp, vp, vp]),
+    "parrot_aligner_create": (C.c_int, [C.POINTER(vp), C.POINTER(AlignerCfg), C.POINTER(AlignerWeights)]),
+    "parrot_aligner_create_ex": (C.c_int, [C.POINTER(vp), C.POINTER(AlignerCfg), C.POINTER(AlignerWeights), i32]),
+    "parrot_aligner_destroy": (None, [vp]),
+    "parrot_aligner_precision": (C.c_int, [vp]),
+    "parrot_aligner_debug_stages": (C.c_int, [vp, vp, vp]),
+    "parrot_aligner_workspace_bytes": (sz, [vp, i32, i32]),
+    "parrot_aligner_forward": (C.c_int, [vp, vp, i32, i32, vp, vp, sz, vp]),
+    "parrot_align_softmax": (C.c_int, [vp, vp, vp, i32, i32, vp, vp]),
+    "parrot_aligner_check": (C.c_int, [vp, vp]),
+    "parrot_aligner_status_async": (C.c_int, [vp, vp, vp]),
+    "parrot_align_workspace_bytes": (sz, [i32, i32, i32]),
+    "parrot_align_durations": (C.c_int, [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, sz, vp]),
 }
 
 _lib = None

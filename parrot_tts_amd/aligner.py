@@ -1,0 +1,297 @@
+"""The forced aligner on the GPU: ``Aligner`` of reference utils/aligner/model.py:24-64, the softmax of
+utils/aligner/extract_durations.py:86-96 and ``extract_durations_with_dijkstra`` of utils/aligner/duration_extraction.py:52-85,
+backed by libparrot_hip.so (``parrot_aligner_forward`` / ``parrot_align_softmax`` / ``parrot_align_durations``).
+
+    Aligner(n_mels, num_symbols, lstm_dim, conv_dim)           the reference's constructor and state_dict keys
+    Aligner.from_checkpoint(checkpoint), .get_step()             as the reference
+    .forward(mel) -> logits (B, T, num_symbols)                 the padded batch as it stands
+    .predict(mel, mel_len) -> pred                              softmax over the real frames, zero beyond
+    .align(mel, mel_len, tokens, tokens_len) -> (durations (B, N) int32, cost (B) fp64, pred)
+    extract_durations_with_dijkstra(tokens, pred) -> durations   numpy in, numpy out, the reference's signature
+
+Padding is NOT masked before the softmax, as in the reference: the backward LSTM of a short row starts inside the padding, so a
+row's logits depend on the length its batch is padded to.  Durations are those of the cheapest monotonic path; among equally cheap
+paths (doubled letters, saturated probabilities) the rule is diagonal, then previous frame, then previous token -- the reference's
+own choice there follows no fixed rule.  There is no CPU path: a CPU tensor raises, as in the other shims."""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Dict, Optional, Tuple
+
+import numpy as np
+import torch
+from torch import nn
+
+from . import _lib
+from .ops import PREC_NAMES, PREC_STR, dptr, param_fingerprint, require_cuda, stream_ptr
+
+MAX_FRAMES, MAX_TOKENS = 32768, 2048  # csrc/aligner.h: ALIGN_MAX_T, ALIGN_MAX_N
+ST_NONFINITE, ST_BAD_INPUT = 5, 9
+BN_EPS = 1e-5
+
+
+def aligner_param_shapes(n_mels: int, num_symbols: int, lstm_dim: int, conv_dim: int) -> Dict[str, tuple]:
+    """state_dict key -> shape of the reference ``Aligner`` (parameters and BatchNorm buffers; ``step`` and the three
+    ``num_batches_tracked`` counters are scalars registered beside them)."""
+    sh = {}
+    for i in range(3):
+        sh[f"convs.{i}.conv.weight"] = (conv_dim, n_mels if i == 0 else conv_dim, 5)
+        for k in ("weight", "bias", "running_mean", "running_var"):
+            sh[f"convs.{i}.bnorm.{k}"] = (conv_dim,)
+    for sfx in ("", "_reverse"):
+        sh["rnn.weight_ih_l0" + sfx] = (4 * lstm_dim, conv_dim)
+        sh["rnn.weight_hh_l0" + sfx] = (4 * lstm_dim, lstm_dim)
+        sh["rnn.bias_ih_l0" + sfx] = (4 * lstm_dim,)
+        sh["rnn.bias_hh_l0" + sfx] = (4 * lstm_dim,)
+    sh["lin.weight"] = (num_symbols, 2 * lstm_dim)
+    sh["lin.bias"] = (num_symbols,)
+    return sh
+
+
+def _attach(root: nn.Module, dotted: str, tensor: torch.Tensor, buffer: bool) -> None:
+    parts = dotted.split(".")
+    m = root
+    for p in parts[:-1]:
+        if p not in m._modules:
+            m.add_module(p, nn.Module())
+        m = m._modules[p]
+    if buffer:
+        m.register_buffer(parts[-1], tensor)
+    else:
+        m.register_parameter(parts[-1], nn.Parameter(tensor))
+
+
+class Aligner(nn.Module):
+    """Inference-only counterpart of the reference's ``Aligner``: the same constructor, ``state_dict`` keys (``step`` and the
+    BatchNorm buffers included), ``from_checkpoint`` and ``get_step``; ``forward`` runs on the HIP kernels.  BatchNorm uses its
+    running statistics (the reference's ``.eval()``); ``step`` increments on every forward, as the reference's does in eval too
+    (``if self.train:`` tests a bound method)."""
+
+    def __init__(self, n_mels: int, num_symbols: int, lstm_dim: int, conv_dim: int, precision=None) -> None:
+        super().__init__()
+        self.n_mels, self.num_symbols, self.lstm_dim, self.conv_dim = int(n_mels), int(num_symbols), int(lstm_dim), int(conv_dim)
+        self.precision = -1 if precision is None else (PREC_NAMES[precision] if isinstance(precision, str) else int(precision))
+        self.register_buffer("step", torch.tensor(1, dtype=torch.int))
+        gen = torch.Generator().manual_seed(0)
+        for key, shape in aligner_param_shapes(self.n_mels, self.num_symbols, self.lstm_dim, self.conv_dim).items():
+            leaf = key.rsplit(".", 1)[1]
+            if leaf in ("running_mean", "running_var"):
+                _attach(self, key, torch.zeros(shape) if leaf == "running_mean" else torch.ones(shape), buffer=True)
+                continue
+            if ".bnorm." in key:
+                t = torch.ones(shape) if leaf == "weight" else torch.zeros(shape)
+            elif len(shape) == 1:
+                t = torch.zeros(shape)
+            else:
+                fan_in = int(np.prod(shape[1:]))
+                t = torch.randn(shape, generator=gen) / max(fan_in, 1) ** 0.5
+            _attach(self, key, t, buffer=False)
+        for i in range(3):
+            _attach(self, f"convs.{i}.bnorm.num_batches_tracked", torch.tensor(0, dtype=torch.long), buffer=True)
+        self._handle: Optional[C.c_void_p] = None
+        self._handle_device = None
+        self._handle_fp = None
+        self._taps = None
+        self.register_load_state_dict_post_hook(lambda module, incompatible: module._invalidate())
+
+    # ---- the reference's surface ---------------------------------------------------------------
+    def get_step(self):
+        return self.step.data.item()
+
+    @classmethod
+    def from_checkpoint(cls, checkpoint: dict) -> "Aligner":
+        config = checkpoint["config"]
+        symbols = checkpoint["symbols"]
+        model = cls(n_mels=config["audio"]["n_mels"], num_symbols=len(symbols) + 1, **config["model"])
+        model.load_state_dict(checkpoint["model"])
+        return model
+
+    # ---- HIP handle ----------------------------------------------------------------------------
+    def _invalidate(self):
+        if self._handle is not None:
+            _lib.lib().parrot_aligner_destroy(self._handle)
+        self._handle = None
+
+    def _apply(self, fn, recurse=True):
+        self._invalidate()
+        return super()._apply(fn, recurse)
+
+    def __del__(self):
+        try:
+            self._invalidate()
+        except Exception:
+            pass
+
+    def _weight_fingerprint(self):
+        step, self._buffers["step"] = self._buffers["step"], None  # (step changes on every forward and is no weight)
+        try:
+            return param_fingerprint(self)
+        finally:
+            self._buffers["step"] = step
+
+    def _current_handle(self, dev):
+        fp = self._weight_fingerprint()
+        if self._handle is None or self._handle_device != dev or self._handle_fp != fp:
+            self._invalidate()
+            self._build(dev)
+            self._handle_fp = fp
+        return self._handle
+
+    def _build(self, device):
+        sd = {k: v.detach().to("cpu", torch.float32).contiguous() for k, v in self.state_dict().items() if v.dim() > 0}
+        P = lambda k: _lib.fptr(sd[k])  # noqa: E731
+        cfg = _lib.AlignerCfg(self.n_mels, self.num_symbols, self.lstm_dim, self.conv_dim, BN_EPS)
+        w = _lib.AlignerWeights()
+        for i in range(3):
+            w.conv_w[i] = P(f"convs.{i}.conv.weight")
+            w.bn_weight[i], w.bn_bias[i] = P(f"convs.{i}.bnorm.weight"), P(f"convs.{i}.bnorm.bias")
+            w.bn_mean[i], w.bn_var[i] = P(f"convs.{i}.bnorm.running_mean"), P(f"convs.{i}.bnorm.running_var")
+        for d, sfx in enumerate(("", "_reverse")):
+            w.w_ih[d], w.w_hh[d] = P("rnn.weight_ih_l0" + sfx), P("rnn.weight_hh_l0" + sfx)
+            w.b_ih[d], w.b_hh[d] = P("rnn.bias_ih_l0" + sfx), P("rnn.bias_hh_l0" + sfx)
+        w.lin_w, w.lin_b = P("lin.weight"), P("lin.bias")
+        hdl = C.c_void_p()
+        with torch.cuda.device(device):
+            _lib.check(_lib.lib().parrot_aligner_create_ex(C.byref(hdl), C.byref(cfg), C.byref(w), self.precision))
+        self._handle, self._handle_device = hdl, device
+
+    @property
+    def precision_in_use(self) -> Optional[str]:
+        """Precision of the live handle ("f16x3", "bf16x6", "f32"; None before the first forward)."""
+        return None if self._handle is None else PREC_STR[int(_lib.lib().parrot_aligner_precision(self._handle))]
+
+    # ---- compute -------------------------------------------------------------------------------
+    def _check_mel(self, mel: torch.Tensor) -> torch.Tensor:
+        require_cuda(mel, "mel")
+        if mel.dim() != 3 or mel.shape[2] != self.n_mels:
+            raise ValueError(f"Aligner: expected mel (B, T, {self.n_mels}), got {tuple(mel.shape)}")
+        if mel.shape[0] < 1 or mel.shape[1] < 1:
+            raise ValueError("Aligner: empty batch or sequence")
+        return mel.to(torch.float32).contiguous()
+
+    @torch.no_grad()
+    def forward(self, mel: torch.Tensor, stages: bool = False):
+        """mel (B, T, n_mels) on the GPU -> logits (B, T, num_symbols).  ``stages=True`` (tests): also the activation after the
+        third BatchNorm, (B, T, conv_dim) as the reference holds it, and the LSTM output (B, T, 2 lstm_dim)."""
+        mel = self._check_mel(mel)
+        dev = mel.device
+        B, T = int(mel.shape[0]), int(mel.shape[1])
+        lib = _lib.lib()
+        logits = torch.empty((B, T, self.num_symbols), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            h = self._current_handle(dev)
+            bn3 = lstm = None
+            if stages:
+                bn3 = torch.empty((B, self.conv_dim, T), dtype=torch.float32, device=dev)
+                lstm = torch.empty((B, T, 2 * self.lstm_dim), dtype=torch.float32, device=dev)
+            _lib.check(lib.parrot_aligner_debug_stages(h, dptr(bn3), dptr(lstm)))
+            n_ws = int(lib.parrot_aligner_workspace_bytes(h, B, T))
+            ws = torch.empty(max(n_ws, 1), dtype=torch.uint8, device=dev)
+            try:
+                _lib.check(lib.parrot_aligner_forward(h, dptr(mel), B, T, dptr(logits), dptr(ws), n_ws, stream_ptr(dev)))
+            finally:
+                if stages:
+                    lib.parrot_aligner_debug_stages(h, None, None)
+        self.step += 1
+        if stages:
+            return logits, {"bn3": bn3.transpose(1, 2).contiguous(), "lstm": lstm}
+        return logits
+
+    @staticmethod
+    def _lengths(x, B: int, hi: int, name: str, dev) -> torch.Tensor:
+        t = torch.as_tensor(x)
+        if tuple(t.shape) != (B,):
+            raise ValueError(f"{name} must hold one length per row ({B}), got {tuple(t.shape)}")
+        if not t.is_cuda and (int(t.min()) < 1 or int(t.max()) > hi):  # (a device tensor is not read back: the kernels set status 9)
+            raise ValueError(f"{name} must lie in [1, {hi}], got {t.tolist()}")
+        return t.to(dev, torch.int32).contiguous()
+
+    @torch.no_grad()
+    def softmax(self, logits: torch.Tensor, mel_len, check: bool = True) -> torch.Tensor:
+        require_cuda(logits, "logits")
+        logits = logits.to(torch.float32).contiguous()
+        dev = logits.device
+        B, T, V = logits.shape
+        if V != self.num_symbols:
+            raise ValueError(f"Aligner.softmax: expected {self.num_symbols} symbols, got {V}")
+        ml = self._lengths(mel_len, B, T, "mel_len", dev)
+        pred = torch.empty_like(logits)
+        with torch.cuda.device(dev):
+            h = self._current_handle(dev)
+            _lib.check(_lib.lib().parrot_align_softmax(h, dptr(logits), dptr(ml), B, T, dptr(pred), stream_ptr(dev)))
+            if check:
+                try:
+                    _lib.check(_lib.lib().parrot_aligner_check(h, stream_ptr(dev)))
+                except _lib.ParrotHipError as e:
+                    if e.code != -1:
+                        raise
+                    raise ValueError(f"mel_len must lie in [1, {T}] (device status {ST_BAD_INPUT})") from e
+        return pred
+
+    def predict(self, mel: torch.Tensor, mel_len, check: bool = True) -> torch.Tensor:
+        """pred (B, T, num_symbols): ``torch.softmax(logits[b, :mel_len[b]], -1)`` per row, zero at and beyond ``mel_len[b]``.
+        Raises when a logit of a real frame is not finite."""
+        return self.softmax(self.forward(mel), mel_len, check=check)
+
+    @staticmethod
+    def durations(pred: torch.Tensor, tokens: torch.Tensor, mel_len, tokens_len) -> torch.Tensor:
+        """Durations (B, N) int32 of ``align_durations`` (the dynamic programme alone, on given probabilities)."""
+        return align_durations(pred, tokens, mel_len, tokens_len)[0]
+
+    def align(self, mel: torch.Tensor, mel_len, tokens: torch.Tensor, tokens_len) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """-> (durations (B, N) int32, cost (B) fp64, pred (B, T, num_symbols)), all on the GPU: row b's durations sum to
+        ``mel_len[b]`` and are zero beyond ``tokens_len[b]``."""
+        pred = self.predict(mel, mel_len)
+        dur, cost = align_durations(pred, tokens, mel_len, tokens_len)
+        return dur, cost, pred
+
+
+@torch.no_grad()
+def align_durations(pred: torch.Tensor, tokens: torch.Tensor, mel_len, tokens_len) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The shortest-path dynamic programme for a ragged batch: pred (B, T, V) fp32 PROBABILITIES on the GPU, tokens (B, N)
+    integer, mel_len / tokens_len (B) -> (durations (B, N) int32, cost (B) fp64).  Raises ValueError for a token outside [0, V)
+    or a length outside its range, FloatingPointError for a NaN / inf probability of a real frame (durations are not returned),
+    ParrotHipError beyond 32768 frames / 2048 tokens."""
+    require_cuda(pred, "pred")
+    if pred.dim() != 3:
+        raise ValueError(f"align_durations: expected pred (B, T, V), got {tuple(pred.shape)}")
+    dev = pred.device
+    pred = pred.to(torch.float32).contiguous()
+    B, T, V = (int(v) for v in pred.shape)
+    tokens = torch.as_tensor(tokens)
+    if tokens.dim() != 2 or tokens.shape[0] != B:
+        raise ValueError(f"align_durations: expected tokens ({B}, N), got {tuple(tokens.shape)}")
+    tokens = tokens.to(dev, torch.int64).contiguous()
+    N = int(tokens.shape[1])
+    ml = Aligner._lengths(mel_len, B, T, "mel_len", dev)
+    tl = Aligner._lengths(tokens_len, B, N, "tokens_len", dev)
+    lib = _lib.lib()
+    dur = torch.empty((B, N), dtype=torch.int32, device=dev)
+    cost = torch.empty((B,), dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        n_ws = int(lib.parrot_align_workspace_bytes(B, T, N))
+        ws = torch.empty(max(n_ws, 4), dtype=torch.uint8, device=dev)
+        _lib.check(lib.parrot_align_durations(dptr(pred), dptr(tokens), dptr(ml), dptr(tl), B, T, V, N, dptr(dur), dptr(cost), dptr(ws),
+                                              n_ws, stream_ptr(dev)))
+        status = int(ws[:4].view(torch.int32).item())
+    if status == ST_BAD_INPUT:
+        raise ValueError(f"align_durations: a token outside [0, {V}) or a length outside [1, T] / [1, N] (device status {status})")
+    if status == ST_NONFINITE:
+        raise FloatingPointError(f"align_durations: a NaN / inf probability in pred (device status {status})")
+    if status:
+        raise RuntimeError(f"align_durations: device status {status}")
+    return dur, cost
+
+
+def extract_durations_with_dijkstra(tokens: np.ndarray, pred: np.ndarray) -> np.ndarray:
+    """Drop-in for reference utils/aligner/duration_extraction.py:52-85: tokens (N,) integer, pred (T, V) probabilities, numpy in,
+    -> durations (N,) int32, numpy out; computed on the current GPU."""
+    tokens = np.asarray(tokens)
+    pred = np.asarray(pred)
+    if tokens.ndim != 1 or pred.ndim != 2 or tokens.size == 0 or pred.shape[0] == 0:
+        raise ValueError(f"extract_durations_with_dijkstra: expected tokens (N,) and pred (T, V), got {tokens.shape} and {pred.shape}")
+    dev = torch.device("cuda", torch.cuda.current_device())
+    p = torch.from_numpy(np.ascontiguousarray(pred, dtype=np.float32)).to(dev)[None]
+    t = torch.from_numpy(np.ascontiguousarray(tokens, dtype=np.int64))[None]
+    dur, _ = align_durations(p, t, [pred.shape[0]], [tokens.shape[0]])
+    return dur[0].cpu().numpy().astype(np.int32)

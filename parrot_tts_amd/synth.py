@@ -7,6 +7,7 @@ the reference's ``state_dict``s:
 * TTE  : keys of ``Parrot.state_dict()``            (reference modules/parrot.py:13-65)
 * vocoder: keys of ``CodeGenerator.state_dict()`` with weight-norm attached
            (``weight_g``/``weight_v``; reference utils/vocoder/models.py:69-130)
+* aligner: keys of ``Aligner.state_dict()``          (reference utils/aligner/model.py:24-40)
 
 Weights come from ``numpy.random.Generator(PCG64(seed))`` so they regenerate bit-identically
 on the GPU box (same image, same numpy); ``state_digest`` lets tests prove that.
@@ -265,6 +266,67 @@ def synth_voc_batch(B: int, U: int, h: dict, seed: int = 0) -> dict:
     code = torch.from_numpy(rng.integers(0, h["num_embeddings"], size=(B, U), dtype=np.int64))
     spkr = torch.from_numpy(rng.integers(0, 10, size=(B, 1), dtype=np.int64))
     return {"code": code, "spkr": spkr}
+
+
+# --------------------------------------------------------------------------------------
+# aligner
+# --------------------------------------------------------------------------------------
+def default_aligner_config(data_dir: str = "runs/aligner/data") -> dict:
+    """Model-relevant part of utils/aligner/aligner_train_config.yaml."""
+    return {
+        "paths": {"dataset_dir": None, "data_dir": data_dir, "symbols_path": None, "metadata_path": "wavs", "dur_path": None},
+        "audio": {"sample_rate": 16000, "n_filters": 1024, "n_mels": 80, "win_length": 1024, "hop_length": 320, "fmin": 0, "fmax": 8000,
+                  "power": 1},
+        "model": {"lstm_dim": 512, "conv_dim": 512},
+        "durations": {"method": "dijkstra"},
+    }
+
+
+def small_aligner_config(data_dir: str = "runs/aligner/data") -> dict:
+    """A reduced aligner (same graph, smaller dims) for fast CPU goldens / smoke tests."""
+    cfg = default_aligner_config(data_dir)
+    cfg["audio"]["n_mels"] = 16
+    cfg["model"].update(lstm_dim=32, conv_dim=32)
+    return cfg
+
+
+def synth_aligner_state_dict(cfg: dict, num_symbols: int, seed: int = 7, gain: float = 1.0) -> Dict[str, torch.Tensor]:
+    """Seeded weights with the key set of the reference ``Aligner.state_dict()`` (utils/aligner/model.py:24-40): ``step``, three
+    bias-free k = 5 convs with BatchNorm parameters AND running statistics (the mean positive: it follows a ReLU), the
+    bidirectional LSTM, the Linear.  ``gain`` scales ``lin.weight``: large values make the softmax peaky, as a trained aligner's."""
+    rng = _rng(seed)
+    n_mels, D, H = cfg["audio"]["n_mels"], cfg["model"]["conv_dim"], cfg["model"]["lstm_dim"]
+    sd: Dict[str, torch.Tensor] = {"step": torch.tensor(1, dtype=torch.int)}
+    for i in range(3):
+        cin = n_mels if i == 0 else D
+        p = f"convs.{i}."
+        sd[p + "conv.weight"] = _normal(rng, (D, cin, 5), 1.4 / math.sqrt(cin * 5))
+        sd[p + "bnorm.weight"] = 1.0 + _normal(rng, (D,), 0.1)
+        sd[p + "bnorm.bias"] = _normal(rng, (D,), 0.05)
+        sd[p + "bnorm.running_mean"] = torch.from_numpy(rng.uniform(0.2, 0.6, size=(D,)).astype(np.float32)).clone()
+        sd[p + "bnorm.running_var"] = torch.from_numpy(rng.uniform(0.3, 1.0, size=(D,)).astype(np.float32)).clone()
+        sd[p + "bnorm.num_batches_tracked"] = torch.tensor(1000, dtype=torch.long)
+    for sfx in ("", "_reverse"):
+        sd["rnn.weight_ih_l0" + sfx] = _normal(rng, (4 * H, D), 1.0 / math.sqrt(D))
+        sd["rnn.weight_hh_l0" + sfx] = _normal(rng, (4 * H, H), 1.0 / math.sqrt(H))
+        sd["rnn.bias_ih_l0" + sfx] = _normal(rng, (4 * H,), 0.1)
+        sd["rnn.bias_hh_l0" + sfx] = _normal(rng, (4 * H,), 0.1)
+    sd["lin.weight"] = _normal(rng, (num_symbols, 2 * H), gain / math.sqrt(2 * H))
+    sd["lin.bias"] = _normal(rng, (num_symbols,), 0.05)
+    return sd
+
+
+def synth_aligner_mel(B: int, T: int, n_mels: int, mel_len=None, seed: int = 0) -> torch.Tensor:
+    """A padded mel batch (B, T, n_mels) as ``collate_dataset`` makes it (utils/aligner/dataset.py:66-75): smooth seeded log-mel-like
+    values, zero beyond ``mel_len[b]``."""
+    rng = _rng(seed)
+    x = rng.standard_normal(size=(B, T + 4, n_mels))
+    x = (x[:, :-4] + x[:, 1:-3] + x[:, 2:-2] + x[:, 3:-1] + x[:, 4:]) * 0.8 - 1.0
+    mel = torch.from_numpy(x.astype(np.float32)).clone()
+    if mel_len is not None:
+        for b, n in enumerate(mel_len):
+            mel[b, int(n):] = 0.0
+    return mel
 
 
 def clone_config(cfg: dict) -> dict:
