@@ -1,5 +1,6 @@
-"""Build libparrot_hip.so in-tree with hipcc for gfx950 (cross-compiles without a GPU).  The kernel templates are
-instantiated in several translation units (csrc/tu_*.hip + parrot_hip.hip) compiled in parallel, then linked."""
+"""Build libparrot_hip.so in-tree with hipcc for gfx950 (cross-compiles without a GPU).  Every csrc/*.hip is one translation unit,
+compiled in parallel, then linked: host_*.hip and parrot_hip.hip (the vocoder) hold the C ABI, one unit per subsystem (shared
+declarations in host_common.h), tu_*.hip instantiate the kernel templates."""
 from __future__ import annotations
 
 import os
@@ -11,7 +12,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libparrot_hip.so")
 OBJ = os.path.join(HERE, "build")
-SOURCES = ["parrot_hip.hip"] + sorted(f for f in os.listdir(CSRC) if f.startswith("tu_") and f.endswith(".hip"))
+SOURCES = sorted(f for f in os.listdir(CSRC) if f.endswith(".hip"))
 HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith(".h")) + [os.path.join("..", "..", "include", h) for h in ("parrot_hip.h", "parrot_hip_debug.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC"]
 # Per-source flags.  tu_split16: LLVM's machine-sink pass moves the weight refills for the next chunk's first k-step -- which feed
@@ -47,7 +48,7 @@ def build(force: bool = False, verbose: bool = False, extra_flags=(), lib_path: 
         subprocess.run(cmd, check=True, cwd=CSRC)
         return obj
 
-    with ThreadPoolExecutor(max_workers=min(len(SOURCES), max(1, (os.cpu_count() or 2) - 1))) as ex:
+    with ThreadPoolExecutor(max_workers=max(1, min(len(SOURCES), 16, (os.cpu_count() or 2) - 1))) as ex:
         objs = list(ex.map(compile_one, SOURCES))
     cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB_OUT] + objs
     if verbose:

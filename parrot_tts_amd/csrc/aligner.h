@@ -2,7 +2,7 @@
 // duration_extraction.py:52-85) that are not parrot_conv plans: the bidirectional LSTM recurrence, the masked softmax, the
 // monotonic shortest-path dynamic programme, and the data movement around the conv plans (transpose, partial-sum / ReLU /
 // BatchNorm-affine epilogue).  The five GEMMs -- three k = 5 convs, the LSTM input projection of both directions for all frames
-// at once, the final Linear -- are parrot_conv plans owned by the parrot_aligner handle (parrot_hip.hip).
+// at once, the final Linear -- are parrot_conv plans owned by the parrot_aligner handle (host_aligner.hip).
 // The launchers below are defined in tu_aligner.hip, which alone sees the kernel bodies (PARROT_ALIGNER_TU).
 #pragma once
 #include <hip/hip_runtime.h>

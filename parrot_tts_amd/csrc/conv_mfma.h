@@ -26,6 +26,8 @@
 #include <stdint.h>
 #include <algorithm>
 
+#include "conv_consts.h"
+
 namespace parrot {
 
 // Samples (at the current layer) of a batch row that holds n real units: n * mul + add for n > 0 -- `add` is what the
@@ -52,10 +54,6 @@ inline hipError_t ensure_dyn_lds(DynLdsOnce& st, const void* kern, size_t lds) {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-enum { PRE_NONE = 0, PRE_LRELU = 1 };
-enum { ACT_NONE = 0, ACT_RELU = 1, ACT_TANH = 2 };
-enum { EPI_STORE = 0, EPI_ADD = 1, EPI_ADD_DIV = 2 };
 
 constexpr int CONV_HALO = 64;  // max (k-1)*dil the fast path supports (MRF needs 50)
 
@@ -559,7 +557,6 @@ __global__ __launch_bounds__(WAVES_M* WAVES_N * 64, MINW) void conv_mfma_kernel(
 struct TileCfg {
     int bm, bn, ci, threads;
 };
-constexpr int NUM_TILE_CFGS = 7;
 __host__ inline TileCfg tile_cfg(int id) {
     switch (id) {
         case 0: return {128, 128, 16, 256};  // waves 2x2, wave 64x64

@@ -10,43 +10,6 @@
 namespace parrot {
 
 // ---------------------------------------------------------------------------------------------
-// vocoder input: x[b, c, t] = c < E ? dict[code[b,t]][c] : spkr[spkr_id[b]][c - E]
-// (utils/vocoder/models.py:155-160 + _upsample :132-151: the speaker vector is repeated over time)
-// grid (ceil(U/64), C/?, B): each block = 64 time steps x 64 channels via an LDS transpose so that
-// both the embedding-row reads (contiguous in c) and the (B,C,U) writes (contiguous in t) coalesce.
-// ---------------------------------------------------------------------------------------------
-static __global__ __launch_bounds__(256) void voc_embed_kernel(const int64_t* __restrict__ code, const int64_t* __restrict__ spkr,
-                                                        const float* __restrict__ dict, const float* __restrict__ spk_tab,
-                                                        float* __restrict__ x, int U, int E, int C, int Cx, int n_emb, int n_spk,
-                                                        int* __restrict__ err, int code_stride) {  // C embedding channels of the Cx input channels; code rows code_stride apart
-    __shared__ float tile[64][65];
-    const int t0 = blockIdx.x * 64, c0 = blockIdx.y * 64, b = blockIdx.z;
-    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;  // 4 rows of 64
-    // load: rows = time, cols = channel (contiguous reads along the embedding row)
-    for (int r = ty; r < 64; r += 4) {
-        const int t = t0 + r, c = c0 + tx;
-        float v = 0.f;
-        if (t < U && c < C) {
-            if (c < E) {
-                int64_t id = code[(size_t)b * code_stride + t];
-                if (id < 0 || id >= n_emb) { atomicExch(err, 1); id = 0; }
-                v = dict[(size_t)id * E + c];
-            } else {
-                int64_t s = spkr[b];
-                if (s < 0 || s >= n_spk) { atomicExch(err, 2); s = 0; }
-                v = spk_tab[(size_t)s * E + (c - E)];
-            }
-        }
-        tile[r][tx] = v;
-    }
-    __syncthreads();
-    for (int r = ty; r < 64; r += 4) {
-        const int c = c0 + r, t = t0 + tx;
-        if (c < C && t < U) x[((size_t)b * Cx + c) * U + t] = tile[tx][r];
-    }
-}
-
-// ---------------------------------------------------------------------------------------------
 // TTE input: x[b, c, s] = tok_emb[phones[b,s]][c] + pe[S][c]   (parrot.py:94-95, fft.py:17-19, Q1)
 // row_len (nullable): row-exact mode, pe[row_len[b]] -- the single row the reference adds when it runs that utterance alone.
 // ---------------------------------------------------------------------------------------------
@@ -244,12 +207,6 @@ static __global__ __launch_bounds__(256) void duration_kernel(const float* __res
         run += (int32_t)dur[(size_t)b * S + s];
         cum[(size_t)b * S + s] = run;
     }
-}
-
-// per-row unit counts re-based to a chunk [lo, lo + n): clamp(len - lo, 0, n)   (parrot_voc_forward_chunked)
-static __global__ void rebase_lens_kernel(const int32_t* __restrict__ lens, int32_t* __restrict__ out, int B, int lo, int n) {
-    const int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b < B) out[b] = min(max(lens[b] - lo, 0), n);
 }
 
 // inclusive prefix sums + totals of given (B,S) durations: parrot_length_regulator (the standalone entry point) and teacher
@@ -668,29 +625,6 @@ static __global__ __launch_bounds__(256) void transpose_cf_to_cl_kernel(const fl
     }
 }
 
-// wav fp32 -> int16 exactly like numpy's `(x * 32768).astype('int16')` for in-range values
-// (C cast: truncation toward zero; utils/vocoder/inference.py:71-73).
-static __global__ void wav_to_int16_kernel(const float* __restrict__ w, int16_t* __restrict__ o, size_t n) {
-    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) o[i] = (int16_t)(int32_t)(w[i] * 32768.0f);
-}
-
-// max |x[i]| -> atomic max into dst[0] (non-negative floats order like their bit patterns); NaN / inf count as +inf
-static __global__ __launch_bounds__(256) void absmax_kernel(const float* __restrict__ x, size_t n, float* __restrict__ dst) {
-    float m = 0.f;
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
-        const float v = fabsf(x[i]);
-        m = (v > m || !(v == v)) ? (v == v ? v : INFINITY) : m;
-    }
-    for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off));
-    if ((threadIdx.x & 63) == 0) atomicMax(reinterpret_cast<int*>(dst), __float_as_int(m));
-}
-
-static __global__ void copy_kernel(const float* __restrict__ a, float* __restrict__ b, size_t n) {
-    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) b[i] = a[i];
-}
-
 
 // the batched fp32 MFMA GEMM of the three-kernel attention path (operand addressing: attn.h)
 struct BgemmParams {
@@ -750,32 +684,6 @@ static __global__ __launch_bounds__(256) void bgemm_mfma_kernel(const BgemmParam
     for (int r = 0; r < 16; ++r) {
         const int m = m0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
         if (m < p.M && n < p.N) C[(long)m * p.ldc + n] = acc[r];
-    }
-}
-
-// MFMA fragment-layout probe: D = A(32x2) * B(2x32) with A[i][k] = i + 100k, B[k][j] = (k ? 1000 : 1) * (j+1)
-// dumps the 16 accumulator registers of every lane so the host can check the assumed C/D mapping.
-static __global__ void mfma_probe_kernel(float* out) {
-    const int lane = threadIdx.x;
-    const int i = lane & 31, k = lane >> 5;
-    const float a = (float)(i + 100 * k);
-    const float b = (k ? 1000.f : 1.f) * (float)(i + 1);
-    f32x16 acc;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, acc, 0, 0, 0);
-#pragma unroll
-    for (int r = 0; r < 16; ++r) out[lane * 16 + r] = acc[r];
-}
-
-// ACT_TANH (conv_post only): applied right after the conv launch (apply_act, conv_mfma.h)
-static __global__ void tanh_inplace_kernel(float* __restrict__ y, size_t n, int* __restrict__ err) {
-    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) {
-        const float v = y[i];
-        y[i] = tanhf(v);
-        // NaN / inf reached the waveform (fp16 split range exceeded).  The PRE-activation is tested: tanhf(+-inf) = +-1 would pass
-        if (err && !(fabsf(v) < INFINITY)) atomicExch(err, 5);
     }
 }
 

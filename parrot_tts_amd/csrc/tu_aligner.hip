@@ -1,5 +1,5 @@
 // tu_aligner.hip -- one translation unit of libparrot_hip.so (parrot_tts_amd/build.py compiles them in parallel): the aligner's
-// kernels (aligner.h) and their launchers.  Shapes are validated by the callers in parrot_hip.hip.
+// kernels (aligner.h) and their launchers.  Shapes are validated by the callers in host_aligner.hip.
 #define PARROT_ALIGNER_TU
 #include "aligner.h"
 namespace parrot {

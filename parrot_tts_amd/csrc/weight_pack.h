@@ -93,6 +93,20 @@ struct WeightAt {
     int m, i, j;
 };
 
+// The exact-fp32 conv adds all c_in * k products of an output along ONE accumulator, an MFMA (2 products) per rounding.  At n_fft =
+// 1024 that chain took the f32 log-mel past 4 x d_ref on white noise; a spec that is exact before its rounding to fp32 leaves 0.25 x
+// (DESIGN.md section 4).  So the PARROT_PREC_F32 plans of the mel handle (DFT) and the aligner run as GROUPED convs: group g sums the
+// g-th G-th of the input channels into its own `rows` rows (padded to whole 128-row tiles: Mg) and a following kernel adds the G
+// partials.  G: the largest count <= 8 that leaves whole 16-channel slabs per group; a c_in that is no multiple of 32 keeps one chain.
+struct ChainGroups { int G, Mg; };
+inline ChainGroups chain_groups(int scheme, int cin, int rows) {
+    int G = 1;
+    if (scheme == PARROT_PREC_F32)
+        for (int g = 8; g > 1 && G == 1; --g)
+            if (cin % (16 * g) == 0) G = g;
+    return {G, G > 1 ? (rows + 127) / 128 * 128 : rows};
+}
+
 // fp32 MFMA fragments: n_steps groups of [lane][4] floats at dst, element (lane, e) of step st = W'(at(st, lane, e))
 template <typename Layout>
 inline void pack_f32(float* dst, size_t n_steps, const GemmWeights& W, Layout at) {

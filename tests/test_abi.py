@@ -37,6 +37,28 @@ def test_every_declared_symbol_is_exported_and_bound(lib):
     assert sorted(_lib.SIGNATURES) == names, "ctypes table and header disagree"
 
 
+def _exported(path, llvm="/opt/rocm/llvm/bin"):
+    """Names the library defines in its dynamic symbol table: llvm-nm -D --defined-only, or -- an LLVM tree that ships without
+    llvm-nm -- the same table through llvm-readelf --dyn-syms (defined = any section index but UND)."""
+    import subprocess
+    nm = os.path.join(llvm, "llvm-nm")
+    if os.path.exists(nm):
+        out = subprocess.run([nm, "-D", "--defined-only", path], check=True, capture_output=True, text=True).stdout
+        return {line.split()[-1] for line in out.splitlines() if line.split()}
+    out = subprocess.run([os.path.join(llvm, "llvm-readelf"), "--dyn-syms", "-W", path], check=True, capture_output=True, text=True).stdout
+    rows = [line.split() for line in out.splitlines()]
+    return {r[7].split("@")[0] for r in rows if len(r) == 8 and r[0].rstrip(":").isdigit() and r[6] != "UND"}
+
+
+def test_exported_c_names_are_exactly_the_declared_ones(lib):
+    """The host side is several translation units whose shared helpers live in namespace parrot (mangled); the only unmangled
+    parrot_* names the library exports are the entry points of the two headers -- no more and no fewer."""
+    from parrot_tts_amd import _lib
+    exported = {n for n in _exported(_lib.LIB_PATH) if n.startswith("parrot_")}
+    assert len(exported) >= 20
+    assert exported == set(_declared() + _declared("parrot_hip_debug.h"))
+
+
 def test_abi_basics(lib):
     assert lib.parrot_abi_version() == 7
     assert lib.parrot_conv_num_tile_cfgs() >= 3

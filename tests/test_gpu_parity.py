@@ -185,7 +185,7 @@ def test_conv1d_fuzz_wide_layers_all_kernel_variants():
 
 def test_conv1d_fuzz_chip_filling_launches_take_the_wide_tiles():
     """The same check on launches of >= 256 workgroups, where conv_split16 picks between its 128 x 128, 128 x 160 and 64 x 128 tiles
-    by rounds x width (parrot_hip.hip / conv_split16.h split16_wide_fits): sequence lengths that leave partial 128- and 160-column
+    by rounds x width (host_conv.hip conv_launch / conv_split16.h split16_wide_fits): sequence lengths that leave partial 128- and 160-column
     tiles, 64 / 128 / 256 rows, residual on and off -- against torch in fp64."""
     rng = _rng(4242)
     for case in range(10):
@@ -392,7 +392,7 @@ def test_vocoder_flags_a_non_finite_waveform():
     g.range_fallback = False  # (the default would rebuild the handle in bf16x6 after this first forward: tests/test_gpu_round4.py)
     y = g(code=code, spkr=spk)
     assert not bool(torch.isfinite(y).all())
-    with pytest.raises(FloatingPointError):
+    with pytest.raises(FloatingPointError, match="vocoder: non-finite output"):
         g.check_inputs()
     ops.set_default_precision(ops.PREC_BF16X6)
     try:
@@ -411,7 +411,7 @@ def test_vocoder_rejects_bad_ids_and_cpu_tensors():
         g(code=torch.zeros(1, 4, dtype=torch.int64), spkr=torch.zeros(1, 1, dtype=torch.int64))
     code = torch.full((1, 4), h["num_embeddings"], dtype=torch.int64, device=DEV)
     g(code=code, spkr=torch.zeros(1, 1, dtype=torch.int64, device=DEV))
-    with pytest.raises(IndexError):
+    with pytest.raises(IndexError, match="vocoder: embedding index out of range"):
         g.check_inputs()
 
 

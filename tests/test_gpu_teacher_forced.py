@@ -276,6 +276,33 @@ def test_teacher_forced_errors(tmp_path):
     assert model.infer(gpu, durations=gpu["duration"])  # the handle is usable after every error
 
 
+def test_c_side_check_reports_bad_durations(tmp_path):
+    """parrot_tte_check itself -- the shim decodes the status word in Python (_raise_status) and never gets there: status 6 and 7 of
+    parrot_tte_set_durations come back as PARROT_E_INVALID with the library's own messages, and reporting clears the flag."""
+    from parrot_tts_amd import _lib
+    from parrot_tts_amd.ops import dptr, stream_ptr
+    cfg = synth.small_tte_config()
+    model = _parrot(cfg, synth.synth_tte_state_dict(cfg, VOCAB, NSPK, seed=5), tmp_path)
+    gpu = {k: v.to(DEV) for k, v in _tf_batch().items()}
+    model(gpu)  # (builds the handle)
+    lib, h, st = _lib.lib(), model._handle, stream_ptr(torch.device(DEV))
+    B, S = gpu["duration"].shape
+    state = torch.empty(lib.parrot_tte_state_bytes(h, B, S), dtype=torch.uint8, device=DEV)
+    out_lens = torch.empty(B, dtype=torch.int32, device=DEV)
+    assert lib.parrot_tte_check(h, st) == 0
+    neg = gpu["duration"].clone()
+    neg[0, 1] = -1
+    assert lib.parrot_tte_set_durations(h, dptr(neg), B, S, None, dptr(out_lens), dptr(state), state.numel(), st) == 0
+    assert lib.parrot_tte_check(h, st) == -1  # PARROT_E_INVALID
+    assert b"tte: repeats can not be negative (a negative duration, duration.py:14)" in lib.parrot_last_error()
+    assert lib.parrot_tte_check(h, st) == 0
+    src_len = gpu["src_mask"].sum(1).to(torch.int32)  # (_tf_batch: row 1 has a nonzero duration at a padded position)
+    assert lib.parrot_tte_set_durations(h, dptr(gpu["duration"]), B, S, dptr(src_len), dptr(out_lens), dptr(state), state.numel(), st) == 0
+    assert lib.parrot_tte_check(h, st) == -1
+    assert b"tte: row-exact durations: a nonzero duration at a padded source position" in lib.parrot_last_error()
+    assert lib.parrot_tte_check(h, st) == 0
+
+
 def test_pipeline_with_durations_vocodes_the_emitted_ids(tmp_path):
     cfg, h = synth.small_tte_config(), synth.small_voc_config()
     sd = synth.synth_tte_state_dict(cfg, VOCAB, NSPK, seed=5)
