@@ -432,6 +432,28 @@ int parrot_aligner_status_async(parrot_aligner_t*, int32_t* dst_dev, void* strea
 size_t parrot_align_workspace_bytes(int32_t B, int32_t T, int32_t N);
 int parrot_align_durations(const float* pred, const int64_t* tokens, const int32_t* mel_len, const int32_t* tokens_len, int32_t B, int32_t T,
                            int32_t V, int32_t N, int32_t* dur_out, double* cost_out, void* ws, size_t ws_bytes, void* stream);
+/* The aligner's validation loss, the CTC loss of utils/aligner/trainer.py:60-63:
+ *   pred = model(mel); pred.transpose(0, 1).log_softmax(2); CTCLoss()(pred, tokens, mel_len, tokens_len)
+ * with torch's defaults (blank = 0, no zero_infinity), forward pass only.  It takes LOGITS: logits (B, T, V) fp32, tokens (B, N)
+ * int64, mel_len / tokens_len (B) int32, all device; row b uses logits[b, :mel_len[b]] and tokens[b, :tokens_len[b]], nothing
+ * beyond them is read.  Per real frame the fp32 max-shifted log-sum-exp over V (the reference's fp32 log_softmax); then, one
+ * workgroup per utterance, the forward recursion over the S = 2 tokens_len + 1 states blank, tok_0, blank, ..., blank in fp64:
+ *   lp[t][c] = logits[t][c] - lse[t];  alpha_0[0] = lp[0][blank], alpha_0[1] = lp[0][tok_0], -inf elsewhere;
+ *   alpha_t[s] = logaddexp(alpha_{t-1}[s], alpha_{t-1}[s-1], alpha_{t-1}[s-2] if s is odd and tok differs from the previous tok)
+ *                + lp[t][label_s];
+ *   nll = -logaddexp(alpha_{T-1}[S-1], alpha_{T-1}[S-2]).
+ * A token equal to the blank is legal.  A row with mel_len < tokens_len + (number of repeated neighbours) has no path: its nll
+ * is exactly +inf and the other rows are untouched.
+ * nll_out (B) fp64; mean_out (1) fp32, nullable: mean_b(nll[b] / tokens_len[b]) (torch's reduction='mean'), summed in fp64 in row
+ * order.  Deterministic: two calls agree bit for bit, and a row's nll does not depend on the rows beside it.
+ * T <= 32768, N <= 2048 (beyond: PARROT_E_UNSUPPORTED; parrot_ctc_workspace_bytes returns 0).
+ * ws: parrot_ctc_workspace_bytes(B, T, N); its first int32 is the call's status: 0; 5, a NaN / inf logit in a real frame; or 9,
+ * a token outside [0, V) among the first tokens_len[b] or a length outside [1, T] / [1, N] -- nothing is read through such a
+ * value and that row's nll is NaN.  The larger status wins. */
+size_t parrot_ctc_workspace_bytes(int32_t B, int32_t T, int32_t N);
+int parrot_ctc_loss(const float* logits, const int64_t* tokens, const int32_t* mel_len, const int32_t* tokens_len, int32_t B, int32_t T,
+                    int32_t V, int32_t N, double* nll_out /* (B) */, float* mean_out /* (1), nullable */, void* ws, size_t ws_bytes,
+                    void* stream);
 
 #ifdef __cplusplus
 }

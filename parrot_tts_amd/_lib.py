@@ -154,6 +154,8 @@ SIGNATURES = {
     "parrot_aligner_status_async": (C.c_int, [vp, vp, vp]),
     "parrot_align_workspace_bytes": (sz, [i32, i32, i32]),
     "parrot_align_durations": (C.c_int, [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, sz, vp]),
+    "parrot_ctc_workspace_bytes": (sz, [i32, i32, i32]),
+    "parrot_ctc_loss": (C.c_int, [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, sz, vp]),
 }
 
 _lib = None

@@ -1,12 +1,15 @@
 """The forced aligner on the GPU: ``Aligner`` of reference utils/aligner/model.py:24-64, the softmax of
 utils/aligner/extract_durations.py:86-96 and ``extract_durations_with_dijkstra`` of utils/aligner/duration_extraction.py:52-85,
-backed by libparrot_hip.so (``parrot_aligner_forward`` / ``parrot_align_softmax`` / ``parrot_align_durations``).
+and the CTC validation loss of utils/aligner/trainer.py:60-63, backed by libparrot_hip.so (``parrot_aligner_forward`` /
+``parrot_align_softmax`` / ``parrot_align_durations`` / ``parrot_ctc_loss``).
 
     Aligner(n_mels, num_symbols, lstm_dim, conv_dim)           the reference's constructor and state_dict keys
     Aligner.from_checkpoint(checkpoint), .get_step()             as the reference
     .forward(mel) -> logits (B, T, num_symbols)                 the padded batch as it stands
     .predict(mel, mel_len) -> pred                              softmax over the real frames, zero beyond
     .align(mel, mel_len, tokens, tokens_len) -> (durations (B, N) int32, cost (B) fp64, pred)
+    .ctc_loss(mel, mel_len, tokens, tokens_len) -> loss          the reference trainer's CTC loss of the batch, forward only
+    ctc_loss(logits, tokens, mel_len, tokens_len) -> loss        the same on given logits
     extract_durations_with_dijkstra(tokens, pred) -> durations   numpy in, numpy out, the reference's signature
 
 Padding is NOT masked before the softmax, as in the reference: the backward LSTM of a short row starts inside the padding, so a
@@ -245,6 +248,37 @@ class Aligner(nn.Module):
         dur, cost = align_durations(pred, tokens, mel_len, tokens_len)
         return dur, cost, pred
 
+    def ctc_loss(self, mel: torch.Tensor, mel_len, tokens: torch.Tensor, tokens_len, reduction: str = "mean") -> torch.Tensor:
+        """The reference trainer's loss of this batch (trainer.py:60-63): ``forward`` on the padded batch as it stands, not
+        masked, then ``ctc_loss`` of the logits."""
+        return ctc_loss(self.forward(mel), tokens, mel_len, tokens_len, reduction=reduction)
+
+
+def _ragged_args(who: str, x: torch.Tensor, name: str, tokens, mel_len, tokens_len):
+    """What ``align_durations`` and ``ctc_loss`` share: x (B, T, V) fp32 on the GPU, tokens (B, N) int64, the lengths (B) int32."""
+    require_cuda(x, name)
+    if x.dim() != 3:
+        raise ValueError(f"{who}: expected {name} (B, T, V), got {tuple(x.shape)}")
+    dev = x.device
+    x = x.to(torch.float32).contiguous()
+    B, T = int(x.shape[0]), int(x.shape[1])
+    tokens = torch.as_tensor(tokens)
+    if tokens.dim() != 2 or tokens.shape[0] != B:
+        raise ValueError(f"{who}: expected tokens ({B}, N), got {tuple(tokens.shape)}")
+    tokens = tokens.to(dev, torch.int64).contiguous()
+    ml = Aligner._lengths(mel_len, B, T, "mel_len", dev)
+    tl = Aligner._lengths(tokens_len, B, int(tokens.shape[1]), "tokens_len", dev)
+    return x, tokens, ml, tl
+
+
+def _raise_status(who: str, status: int, V: int, what: str) -> None:
+    if status == ST_BAD_INPUT:
+        raise ValueError(f"{who}: a token outside [0, {V}) or a length outside [1, T] / [1, N] (device status {status})")
+    if status == ST_NONFINITE:
+        raise FloatingPointError(f"{who}: a NaN / inf {what} (device status {status})")
+    if status:
+        raise RuntimeError(f"{who}: device status {status}")
+
 
 @torch.no_grad()
 def align_durations(pred: torch.Tensor, tokens: torch.Tensor, mel_len, tokens_len) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -252,19 +286,9 @@ def align_durations(pred: torch.Tensor, tokens: torch.Tensor, mel_len, tokens_le
     integer, mel_len / tokens_len (B) -> (durations (B, N) int32, cost (B) fp64).  Raises ValueError for a token outside [0, V)
     or a length outside its range, FloatingPointError for a NaN / inf probability of a real frame (durations are not returned),
     ParrotHipError beyond 32768 frames / 2048 tokens."""
-    require_cuda(pred, "pred")
-    if pred.dim() != 3:
-        raise ValueError(f"align_durations: expected pred (B, T, V), got {tuple(pred.shape)}")
+    pred, tokens, ml, tl = _ragged_args("align_durations", pred, "pred", tokens, mel_len, tokens_len)
     dev = pred.device
-    pred = pred.to(torch.float32).contiguous()
-    B, T, V = (int(v) for v in pred.shape)
-    tokens = torch.as_tensor(tokens)
-    if tokens.dim() != 2 or tokens.shape[0] != B:
-        raise ValueError(f"align_durations: expected tokens ({B}, N), got {tuple(tokens.shape)}")
-    tokens = tokens.to(dev, torch.int64).contiguous()
-    N = int(tokens.shape[1])
-    ml = Aligner._lengths(mel_len, B, T, "mel_len", dev)
-    tl = Aligner._lengths(tokens_len, B, N, "tokens_len", dev)
+    (B, T, V), N = (int(v) for v in pred.shape), int(tokens.shape[1])
     lib = _lib.lib()
     dur = torch.empty((B, N), dtype=torch.int32, device=dev)
     cost = torch.empty((B,), dtype=torch.float64, device=dev)
@@ -274,13 +298,36 @@ def align_durations(pred: torch.Tensor, tokens: torch.Tensor, mel_len, tokens_le
         _lib.check(lib.parrot_align_durations(dptr(pred), dptr(tokens), dptr(ml), dptr(tl), B, T, V, N, dptr(dur), dptr(cost), dptr(ws),
                                               n_ws, stream_ptr(dev)))
         status = int(ws[:4].view(torch.int32).item())
-    if status == ST_BAD_INPUT:
-        raise ValueError(f"align_durations: a token outside [0, {V}) or a length outside [1, T] / [1, N] (device status {status})")
-    if status == ST_NONFINITE:
-        raise FloatingPointError(f"align_durations: a NaN / inf probability in pred (device status {status})")
-    if status:
-        raise RuntimeError(f"align_durations: device status {status}")
+    _raise_status("align_durations", status, V, "probability in pred")
     return dur, cost
+
+
+@torch.no_grad()
+def ctc_loss(logits: torch.Tensor, tokens: torch.Tensor, mel_len, tokens_len, reduction: str = "mean") -> torch.Tensor:
+    """``CTCLoss()(logits.transpose(0, 1).log_softmax(2), tokens, mel_len, tokens_len)`` of utils/aligner/trainer.py:60-63 (blank
+    0, no zero_infinity) for a ragged batch, forward only: logits (B, T, V) fp32 LOGITS on the GPU, tokens (B, N) integer, mel_len
+    / tokens_len (B).  The log-sum-exp over V is fp32, the recursion fp64.  ``reduction``: "mean" -> 0-dim fp32,
+    mean_b(nll[b] / tokens_len[b]) as torch's; "none" -> nll (B) fp64; "sum" -> 0-dim fp64.  A row that has no path (mel_len <
+    tokens_len + repeated neighbours) is +inf.  Raises ValueError for a token outside [0, V) or a length outside its range,
+    FloatingPointError for a NaN / inf logit of a real frame, ParrotHipError beyond 32768 frames / 2048 tokens."""
+    if reduction not in ("mean", "none", "sum"):
+        raise ValueError(f"ctc_loss: reduction must be 'mean', 'none' or 'sum', got {reduction!r}")
+    logits, tokens, ml, tl = _ragged_args("ctc_loss", logits, "logits", tokens, mel_len, tokens_len)
+    dev = logits.device
+    (B, T, V), N = (int(v) for v in logits.shape), int(tokens.shape[1])
+    lib = _lib.lib()
+    nll = torch.empty((B,), dtype=torch.float64, device=dev)
+    mean = torch.empty((), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        n_ws = int(lib.parrot_ctc_workspace_bytes(B, T, N))
+        ws = torch.empty(max(n_ws, 4), dtype=torch.uint8, device=dev)
+        _lib.check(lib.parrot_ctc_loss(dptr(logits), dptr(tokens), dptr(ml), dptr(tl), B, T, V, N, dptr(nll), dptr(mean), dptr(ws), n_ws,
+                                       stream_ptr(dev)))
+        status = int(ws[:4].view(torch.int32).item())
+    _raise_status("ctc_loss", status, V, "logit in a real frame")
+    if reduction == "mean":
+        return mean
+    return nll if reduction == "none" else nll.sum()
 
 
 def extract_durations_with_dijkstra(tokens: np.ndarray, pred: np.ndarray) -> np.ndarray:

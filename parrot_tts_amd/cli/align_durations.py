@@ -70,56 +70,73 @@ def load_item(item, mel_dir: Path, token_dir: Path, n_mels: int):
     return mel.astype(np.float32), tokens[:tokens_len]
 
 
-def run(args, model_loader=load_model, device=None) -> dict:
-    config = read_config(args.config)
-    method = config.get("durations", {}).get("method", "dijkstra")
-    if method == "beam":
-        raise SystemExit("align_durations: durations.method 'beam' is not covered (INTEGRATION.md); use 'dijkstra'")
+def open_corpus(config: dict, model_path, model_loader, device):
+    """What the aligner's drivers read (extract_durations.py:60-84): the checkpoint (default
+    ``<data_dir>/checkpoints/latest_model.pt``) with its symbols assertion, ``dataset.pkl``, and where the mels and tokens lie.
+    -> (data_dir, model, dataset, n_mels, mel_dir, token_dir)"""
     data_dir = Path(config["paths"]["data_dir"])
-    model_path = Path(args.model) if args.model else data_dir / "checkpoints" / "latest_model.pt"
-    target = data_dir / args.target
-    dur_dir, pred_dir = target / "durations", target / "predictions"
-    dur_dir.mkdir(parents=True, exist_ok=True)
-    pred_dir.mkdir(parents=True, exist_ok=True)
-    device = torch.device("cuda") if device is None else torch.device(device)
+    model_path = Path(model_path) if model_path else data_dir / "checkpoints" / "latest_model.pt"
     checkpoint = torch.load(model_path, map_location=torch.device("cpu"), weights_only=False)
     symbols = unpickle(data_dir / "symbols.pkl")
     assert symbols == checkpoint["symbols"], "Symbols from dataset do not match symbols from model checkpoint!"
     model = model_loader(checkpoint, device)
     dataset = unpickle(data_dir / "dataset.pkl")
-    n_mels = int(checkpoint["config"]["audio"]["n_mels"])
-    mel_dir, token_dir = data_dir / "mels", data_dir / "tokens"
+    return data_dir, model, dataset, int(checkpoint["config"]["audio"]["n_mels"]), data_dir / "mels", data_dir / "tokens"
+
+
+def load_batch(dataset, idx, mel_dir: Path, token_dir: Path, n_mels: int):
+    """The loadable items of one batch, zero-padded to the batch's own longest mel and token row.  A failing item is reported and
+    left out (extract_durations.py:43-45).  -> (items, mel (B, T, n_mels) fp32, tokens (B, N) int64, mel_len, tokens_len, n_failed),
+    the tensors on the host; ``items`` is empty when nothing loaded."""
+    rows, n_failed = [], 0
+    for i in idx:
+        try:
+            rows.append((dataset[i],) + load_item(dataset[i], mel_dir, token_dir, n_mels))
+        except Exception as e:
+            print(f"Error processing {dataset[i].get('item_id')}: {e}", file=sys.stderr)
+            n_failed += 1
+    if not rows:
+        return [], None, None, [], [], n_failed
+    mel_len = [int(r[0]["mel_len"]) for r in rows]
+    tokens_len = [int(r[2].shape[0]) for r in rows]
+    mel = torch.zeros((len(rows), max(mel_len), n_mels), dtype=torch.float32)
+    tokens = torch.zeros((len(rows), max(tokens_len)), dtype=torch.int64)
+    for b, (_, m, t) in enumerate(rows):
+        mel[b, :mel_len[b]] = torch.from_numpy(m[:mel_len[b]])
+        tokens[b, :tokens_len[b]] = torch.from_numpy(t)
+    return [r[0] for r in rows], mel, tokens, mel_len, tokens_len, n_failed
+
+
+def run(args, model_loader=load_model, device=None) -> dict:
+    config = read_config(args.config)
+    method = config.get("durations", {}).get("method", "dijkstra")
+    if method == "beam":
+        raise SystemExit("align_durations: durations.method 'beam' is not covered (INTEGRATION.md); use 'dijkstra'")
+    device = torch.device("cuda") if device is None else torch.device(device)
+    target = Path(config["paths"]["data_dir"]) / args.target
+    dur_dir, pred_dir = target / "durations", target / "predictions"
+    dur_dir.mkdir(parents=True, exist_ok=True)
+    pred_dir.mkdir(parents=True, exist_ok=True)
+    data_dir, model, dataset, n_mels, mel_dir, token_dir = open_corpus(config, args.model, model_loader, device)
     batches = plan_batches(len(dataset), max(1, int(args.batch_size)))
     n_written = n_failed = 0
     for idx in batches:
-        rows = []
-        for i in idx:
-            try:
-                rows.append((dataset[i],) + load_item(dataset[i], mel_dir, token_dir, n_mels))
-            except Exception as e:  # (extract_durations.py:43-45)
-                print(f"Error processing {dataset[i].get('item_id')}: {e}", file=sys.stderr)
-                n_failed += 1
-        if not rows:
+        items, mel, tokens, mel_len, tokens_len, failed = load_batch(dataset, idx, mel_dir, token_dir, n_mels)
+        n_failed += failed
+        if not items:
             continue
-        mel_len = [int(r[0]["mel_len"]) for r in rows]
-        tokens_len = [int(r[2].shape[0]) for r in rows]
-        mel = torch.zeros((len(rows), max(mel_len), n_mels), dtype=torch.float32)
-        tokens = torch.zeros((len(rows), max(tokens_len)), dtype=torch.int64)
-        for b, (_, m, t) in enumerate(rows):
-            mel[b, :mel_len[b]] = torch.from_numpy(m[:mel_len[b]])
-            tokens[b, :tokens_len[b]] = torch.from_numpy(t)
         try:
             pred = model.predict(mel.to(device), mel_len)
         except Exception as e:
-            print(f"Error processing {[r[0]['item_id'] for r in rows]}: {e}", file=sys.stderr)
-            n_failed += len(rows)
+            print(f"Error processing {[it['item_id'] for it in items]}: {e}", file=sys.stderr)
+            n_failed += len(items)
             continue
         try:
             dur = model.durations(pred, tokens.to(device), mel_len, tokens_len).cpu().numpy()
         except Exception:  # one bad item (a token outside the symbol table ...) fails the call: find it row by row, same pred
             dur = None
         pred_h = pred.cpu().numpy()
-        for b, (item, _, _) in enumerate(rows):
+        for b, item in enumerate(items):
             try:
                 np.save(pred_dir / f"{item['item_id']}.npy", pred_h[b, :mel_len[b]], allow_pickle=False)  # (kept when the durations fail, as the reference's)
                 d_b = dur[b] if dur is not None else model.durations(pred[b:b + 1], tokens[b:b + 1].to(device), mel_len[b:b + 1],

@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "aligner.h"
+#include "ctc.h"
 #include "weight_pack.h"
 
 using namespace parrot;
@@ -220,6 +221,28 @@ extern "C" int parrot_align_durations(const float* pred, const int64_t* tokens, 
     }
     HIP_TRY(hipMemsetAsync(ws, 0, sizeof(int), s));
     HIP_TRY(launch_align_dp(pred, tokens, mel_len, tokens_len, B, T, V, N, (uint8_t*)ws + 256, dur_out, cost_out, (int*)ws, s));
+    return PARROT_OK;
+}
+extern "C" size_t parrot_ctc_workspace_bytes(int32_t B, int32_t T, int32_t N) {
+    if (B <= 0 || B > 65535 || T <= 0 || T > ALIGN_MAX_T || N <= 0 || N > ALIGN_MAX_N) return 0;
+    return 256 + align_up((size_t)B * T * sizeof(double), 256);  // the status word, then lse (B, T) fp64
+}
+extern "C" int parrot_ctc_loss(const float* logits, const int64_t* tokens, const int32_t* mel_len, const int32_t* tokens_len, int32_t B, int32_t T,
+                               int32_t V, int32_t N, double* nll_out, float* mean_out, void* ws, size_t ws_bytes, void* stream) {
+    if (!logits || !tokens || !mel_len || !tokens_len || !nll_out || !ws) return fail(PARROT_E_INVALID, "ctc_loss: null argument");
+    if (B <= 0 || B > 65535 || T <= 0 || N <= 0 || V <= 0) return fail(PARROT_E_INVALID, "ctc_loss: need 1 <= B <= 65535 and T, N, V >= 1");
+    if (T > ALIGN_MAX_T || N > ALIGN_MAX_N) return fail(PARROT_E_UNSUPPORTED, "ctc_loss: at most 32768 frames and 2048 tokens per utterance");
+    if (ws_bytes < parrot_ctc_workspace_bytes(B, T, N)) return fail(PARROT_E_NOMEM, "ctc_loss: workspace too small");
+    hipStream_t s = (hipStream_t)stream;
+    if (poison_word()) {
+        TRY(poison(ws, ws_bytes, s));
+        TRY(poison(nll_out, (size_t)B * sizeof(double), s));
+        if (mean_out) TRY(poison(mean_out, sizeof(float), s));
+    }
+    HIP_TRY(hipMemsetAsync(ws, 0, sizeof(int), s));
+    double* lse = (double*)((char*)ws + 256);
+    HIP_TRY(launch_ctc_lse(logits, mel_len, lse, B, T, V, (int*)ws, s));
+    HIP_TRY(launch_ctc_alpha(logits, tokens, mel_len, tokens_len, lse, B, T, V, N, nll_out, mean_out, (int*)ws, s));
     return PARROT_OK;
 }
 static int aligner_status(int h) {
