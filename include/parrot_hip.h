@@ -454,6 +454,28 @@ size_t parrot_ctc_workspace_bytes(int32_t B, int32_t T, int32_t N);
 int parrot_ctc_loss(const float* logits, const int64_t* tokens, const int32_t* mel_len, const int32_t* tokens_len, int32_t B, int32_t T,
                     int32_t V, int32_t N, double* nll_out /* (B) */, float* mean_out /* (1), nullable */, void* ws, size_t ws_bytes,
                     void* stream);
+/* The same loss with its gradient with respect to the LOGITS (the log-softmax folded in): what loss.backward() of
+ * utils/aligner/trainer.py:60-71 hands to the network.  Arguments, limits, status word and error codes are parrot_ctc_loss's;
+ * nll_out holds the same bits.  The call is stateless: it recomputes alpha, keeps it, runs the mirror-image recursion
+ *   beta_{T-1}[S-1] = lp[T-1][blank], beta_{T-1}[S-2] = lp[T-1][label_{S-2}], -inf elsewhere;
+ *   beta_t[s] = logaddexp(beta_{t+1}[s], beta_{t+1}[s+1], beta_{t+1}[s+2] if state s+2 may be entered by a skip) + lp[t][label_s]
+ * in fp64 and writes, for every row b, frame t and symbol v,
+ *   gamma_t(v)    = sum over the states s labelled v of exp(alpha_t[s] + beta_t[s] - lp[t][v] + nll[b]),
+ *   grad[b][t][v] = (float)(w_b (exp(lp[t][v]) - gamma_t(v)))   for t < mel_len[b],        exactly 0 for mel_len[b] <= t < T,
+ * with w_b = row_weight[b] (fp64, device; null: all ones) -- the caller's reduction and upstream gradient.  Every element of
+ * grad_out (B, T, V) fp32 is written.  This is the true gradient: torch's CPU backward drops the final blank state's term at
+ * the last frame of a row whose last token is the blank, and differs there.
+ * Special rows: a row without a path (nll = +inf) is NaN on its real frames and 0 beyond them, as torch's; with zero_infinity
+ * != 0 it is 0 throughout.  A row that raised status 9 is NaN throughout, and nothing is read through the bad value.  Other rows
+ * are untouched by either.
+ * Deterministic: no floating-point atomics; every gamma_t(v) is summed in an order fixed by the row's tokens, so two calls agree
+ * bit for bit and a row's gradient depends on that row, T and V only -- not on B or on the rows beside it.
+ * ws: parrot_ctc_grad_workspace_bytes(B, T, V, N) (0 beyond the limits): the status word, lse, alpha (B, T, 2 N + 1) fp64 and
+ * the sorted token index. */
+size_t parrot_ctc_grad_workspace_bytes(int32_t B, int32_t T, int32_t V, int32_t N);
+int parrot_ctc_loss_grad(const float* logits, const int64_t* tokens, const int32_t* mel_len, const int32_t* tokens_len, int32_t B,
+                         int32_t T, int32_t V, int32_t N, const double* row_weight /* (B), nullable: all ones */, int32_t zero_infinity,
+                         double* nll_out /* (B) */, float* grad_out /* (B, T, V) */, void* ws, size_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -156,6 +156,8 @@ SIGNATURES = {
     "parrot_align_durations": (C.c_int, [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, sz, vp]),
     "parrot_ctc_workspace_bytes": (sz, [i32, i32, i32]),
     "parrot_ctc_loss": (C.c_int, [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, sz, vp]),
+    "parrot_ctc_grad_workspace_bytes": (sz, [i32, i32, i32, i32]),
+    "parrot_ctc_loss_grad": (C.c_int, [vp, vp, vp, vp, i32, i32, i32, i32, vp, i32, vp, vp, vp, sz, vp]),
 }
 
 _lib = None

@@ -1,7 +1,7 @@
 """The forced aligner on the GPU: ``Aligner`` of reference utils/aligner/model.py:24-64, the softmax of
 utils/aligner/extract_durations.py:86-96 and ``extract_durations_with_dijkstra`` of utils/aligner/duration_extraction.py:52-85,
-and the CTC validation loss of utils/aligner/trainer.py:60-63, backed by libparrot_hip.so (``parrot_aligner_forward`` /
-``parrot_align_softmax`` / ``parrot_align_durations`` / ``parrot_ctc_loss``).
+and the CTC loss of utils/aligner/trainer.py:60-71 with its gradient, backed by libparrot_hip.so (``parrot_aligner_forward`` /
+``parrot_align_softmax`` / ``parrot_align_durations`` / ``parrot_ctc_loss`` / ``parrot_ctc_loss_grad``).
 
     Aligner(n_mels, num_symbols, lstm_dim, conv_dim)           the reference's constructor and state_dict keys
     Aligner.from_checkpoint(checkpoint), .get_step()             as the reference
@@ -10,6 +10,9 @@ and the CTC validation loss of utils/aligner/trainer.py:60-63, backed by libparr
     .align(mel, mel_len, tokens, tokens_len) -> (durations (B, N) int32, cost (B) fp64, pred)
     .ctc_loss(mel, mel_len, tokens, tokens_len) -> loss          the reference trainer's CTC loss of the batch, forward only
     ctc_loss(logits, tokens, mel_len, tokens_len) -> loss        the same on given logits
+    ctc_loss_and_grad(logits, tokens, mel_len, tokens_len) -> (loss, grad)   the loss and d loss / d logits in one call
+    ctc_loss_trainable(logits, tokens, mel_len, tokens_len) -> loss           the loss as an autograd node (logits only)
+    CTCLoss(blank=0, reduction="mean", zero_infinity=False)      torch.nn.CTCLoss's call shape over ctc_loss_trainable
     extract_durations_with_dijkstra(tokens, pred) -> durations   numpy in, numpy out, the reference's signature
 
 Padding is NOT masked before the softmax, as in the reference: the backward LSTM of a short row starts inside the padding, so a
@@ -328,6 +331,126 @@ def ctc_loss(logits: torch.Tensor, tokens: torch.Tensor, mel_len, tokens_len, re
     if reduction == "mean":
         return mean
     return nll if reduction == "none" else nll.sum()
+
+
+def ctc_reduction_weights(tokens_len: torch.Tensor, reduction: str) -> torch.Tensor:
+    """d loss / d nll[b] of torch's reductions, (B) fp64 on ``tokens_len``'s device: 1 for "none" and "sum"; 1 / (max(N_b, 1) B) for
+    "mean", formed as torch's autograd forms it, (1 / B) / max(N_b, 1)."""
+    if reduction not in ("mean", "none", "sum"):
+        raise ValueError(f"ctc_loss: reduction must be 'mean', 'none' or 'sum', got {reduction!r}")
+    B = int(tokens_len.shape[0])
+    w = torch.ones((B,), dtype=torch.float64, device=tokens_len.device)
+    if reduction == "mean":
+        w = w / B / tokens_len.clamp_min(1).to(torch.float64)
+    return w
+
+
+def _reduce_nll(nll: torch.Tensor, tl: torch.Tensor, reduction: str, zero_infinity: bool) -> torch.Tensor:
+    """``ctc_loss``'s three results from nll (B) fp64, bit for bit: "mean" is the fp64 sum of nll / tokens_len in row order, over B,
+    rounded to fp32 once (csrc/ctc.h ctc_mean_kernel; the running sum is formed on the host, the call has just read the status back
+    anyway).  ``zero_infinity``: a row without a path counts 0."""
+    if zero_infinity:
+        nll = torch.where(torch.isinf(nll), torch.zeros_like(nll), nll)
+    if reduction == "none":
+        return nll
+    if reduction == "sum":
+        return nll.sum()
+    with np.errstate(invalid="ignore"):
+        terms = nll.cpu().numpy() / tl.cpu().numpy().astype(np.float64)
+        mean = np.float32(np.cumsum(terms)[-1] / np.float64(terms.shape[0]))  # (cumsum: strictly in row order)
+    return torch.tensor(mean, dtype=torch.float32, device=nll.device)
+
+
+def _ctc_grad_call(logits, tokens, ml, tl, row_weight, zero_infinity: bool) -> Tuple[torch.Tensor, torch.Tensor]:
+    """parrot_ctc_loss_grad on validated arguments -> (nll (B) fp64, grad (B, T, V) fp32); raises as ``ctc_loss``."""
+    dev = logits.device
+    (B, T, V), N = (int(v) for v in logits.shape), int(tokens.shape[1])
+    lib = _lib.lib()
+    nll = torch.empty((B,), dtype=torch.float64, device=dev)
+    grad = torch.empty((B, T, V), dtype=torch.float32, device=dev)
+    row_weight = row_weight.to(dev, torch.float64).contiguous()
+    with torch.cuda.device(dev):
+        n_ws = int(lib.parrot_ctc_grad_workspace_bytes(B, T, V, N))
+        ws = torch.empty(max(n_ws, 4), dtype=torch.uint8, device=dev)
+        _lib.check(lib.parrot_ctc_loss_grad(dptr(logits), dptr(tokens), dptr(ml), dptr(tl), B, T, V, N, dptr(row_weight), int(bool(zero_infinity)),
+                                            dptr(nll), dptr(grad), dptr(ws), n_ws, stream_ptr(dev)))
+        status = int(ws[:4].view(torch.int32).item())
+    _raise_status("ctc_loss_and_grad", status, V, "logit in a real frame")
+    return nll, grad
+
+
+@torch.no_grad()
+def ctc_loss_and_grad(logits: torch.Tensor, tokens: torch.Tensor, mel_len, tokens_len, reduction: str = "mean",
+                      zero_infinity: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``ctc_loss`` and its gradient with respect to the logits in one call (trainer.py:60-71: the loss and ``loss.backward()``):
+    -> (loss, grad (B, T, V) fp32).  ``loss`` is ``ctc_loss(..., reduction)``, bit for bit; ``grad[b] = w_b d nll[b] / d logits[b]``
+    with w_b = 1 for "none" / "sum" and 1 / (max(N_b, 1) B) for "mean" (torch's rule), exactly 0 at and beyond ``mel_len[b]``.  The
+    recursions are fp64 and nothing is accumulated atomically: two calls agree bit for bit and a row's gradient does not depend on
+    the rows beside it.  A row without a path: loss +inf and NaN on its real frames, as torch's; with ``zero_infinity`` it counts
+    0 and its gradient is 0.  Unlike torch's CPU backward this is the true gradient also for a row whose last token is the
+    blank (0).  Raises as ``ctc_loss``."""
+    if reduction not in ("mean", "none", "sum"):
+        raise ValueError(f"ctc_loss_and_grad: reduction must be 'mean', 'none' or 'sum', got {reduction!r}")
+    logits, tokens, ml, tl = _ragged_args("ctc_loss_and_grad", logits, "logits", tokens, mel_len, tokens_len)
+    nll, grad = _ctc_grad_call(logits, tokens, ml, tl, ctc_reduction_weights(tl, reduction), zero_infinity)
+    return _reduce_nll(nll, tl, reduction, zero_infinity), grad
+
+
+class _CtcLossFn(torch.autograd.Function):
+    """The forward is ``ctc_loss``; the backward is one parrot_ctc_loss_grad call with row_weight = grad_output x the reduction's
+    weight.  Only the logits get a gradient, and there is no double backward."""
+
+    @staticmethod
+    def forward(ctx, logits, tokens, mel_len, tokens_len, reduction, zero_infinity):
+        x, tokens, ml, tl = _ragged_args("ctc_loss_trainable", logits, "logits", tokens, mel_len, tokens_len)
+        ctx.save_for_backward(x, tokens, ml, tl)
+        ctx.reduction, ctx.zero_infinity, ctx.in_dtype = reduction, bool(zero_infinity), logits.dtype
+        if not zero_infinity:
+            return ctc_loss(x, tokens, ml, tl, reduction=reduction)
+        return _reduce_nll(ctc_loss(x, tokens, ml, tl, reduction="none"), tl, reduction, True)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_output):
+        x, tokens, ml, tl = ctx.saved_tensors
+        w = ctc_reduction_weights(tl, ctx.reduction) * grad_output.detach().to(x.device, torch.float64)  # (a 0-dim grad_output broadcasts)
+        _, grad = _ctc_grad_call(x, tokens, ml, tl, w, ctx.zero_infinity)
+        return grad.to(ctx.in_dtype), None, None, None, None, None
+
+
+def ctc_loss_trainable(logits: torch.Tensor, tokens: torch.Tensor, mel_len, tokens_len, reduction: str = "mean",
+                       zero_infinity: bool = False) -> torch.Tensor:
+    """``ctc_loss`` as a differentiable function of the logits: same values and dtypes ("mean" 0-dim fp32, "none" (B) fp64, "sum"
+    0-dim fp64), and ``.backward()`` runs ``parrot_ctc_loss_grad`` -- deterministic, so it also runs under
+    ``torch.use_deterministic_algorithms(True)``, where torch's own device backward raises.  For a torch-built model: the HIP
+    ``Aligner.forward`` has no backward.  No double backward."""
+    if reduction not in ("mean", "none", "sum"):
+        raise ValueError(f"ctc_loss_trainable: reduction must be 'mean', 'none' or 'sum', got {reduction!r}")
+    return _CtcLossFn.apply(logits, tokens, mel_len, tokens_len, reduction, zero_infinity)
+
+
+class CTCLoss(nn.Module):
+    """``torch.nn.CTCLoss`` for the reference trainer (trainer.py:21 becomes ``from parrot_tts_amd.aligner import CTCLoss``):
+    ``forward(log_probs (T, B, V), targets (B, N), input_lengths (B), target_lengths (B))``.  The input is transposed to (B, T, V)
+    and taken as LOGITS: normalising log-probabilities again changes them by the fp32 log-sum-exp's rounding only, and the gradient
+    returned for ``log_probs`` is the one torch returns (softmax minus occupancy).  Result dtypes follow ``ctc_loss``, not torch:
+    "mean" is fp32, "none" and "sum" are fp64.  Only ``blank=0``, padded 2-D targets and batched input exist here; anything else
+    raises and is never approximated."""
+
+    def __init__(self, blank: int = 0, reduction: str = "mean", zero_infinity: bool = False) -> None:
+        super().__init__()
+        if blank != 0:
+            raise ValueError(f"CTCLoss: only blank=0 is implemented, got {blank}")
+        if reduction not in ("mean", "none", "sum"):
+            raise ValueError(f"CTCLoss: reduction must be 'mean', 'none' or 'sum', got {reduction!r}")
+        self.blank, self.reduction, self.zero_infinity = 0, reduction, bool(zero_infinity)
+
+    def forward(self, log_probs: torch.Tensor, targets: torch.Tensor, input_lengths, target_lengths) -> torch.Tensor:
+        if log_probs.dim() != 3:
+            raise NotImplementedError(f"CTCLoss: expected batched log_probs (T, B, V), got {tuple(log_probs.shape)}")
+        if torch.as_tensor(targets).dim() != 2:
+            raise NotImplementedError("CTCLoss: expected padded targets (B, N); 1-D concatenated targets are not implemented")
+        return ctc_loss_trainable(log_probs.transpose(0, 1), targets, input_lengths, target_lengths, self.reduction, self.zero_infinity)
 
 
 def extract_durations_with_dijkstra(tokens: np.ndarray, pred: np.ndarray) -> np.ndarray:

@@ -242,7 +242,49 @@ extern "C" int parrot_ctc_loss(const float* logits, const int64_t* tokens, const
     HIP_TRY(hipMemsetAsync(ws, 0, sizeof(int), s));
     double* lse = (double*)((char*)ws + 256);
     HIP_TRY(launch_ctc_lse(logits, mel_len, lse, B, T, V, (int*)ws, s));
-    HIP_TRY(launch_ctc_alpha(logits, tokens, mel_len, tokens_len, lse, B, T, V, N, nll_out, mean_out, (int*)ws, s));
+    HIP_TRY(launch_ctc_alpha(logits, tokens, mel_len, tokens_len, lse, B, T, V, N, nll_out, mean_out, nullptr, (int*)ws, s));
+    return PARROT_OK;
+}
+// the gradient's workspace: the status word, lse (B, T) fp64, alpha / log-occupancy (B, T, 2 N + 1) fp64, then the sorted token
+// positions (B, N) and each label's segment of them, seg_lo and seg_hi (B, V) int32
+struct CtcGradLayout {
+    size_t lse, occ, order, seg_lo, seg_hi, total;
+};
+static CtcGradLayout ctc_grad_layout(int32_t B, int32_t T, int32_t V, int32_t N) {
+    CtcGradLayout l{};
+    l.lse = 256;
+    l.occ = l.lse + align_up((size_t)B * T * sizeof(double), 256);
+    l.order = l.occ + align_up((size_t)B * T * ((size_t)2 * N + 1) * sizeof(double), 256);
+    l.seg_lo = l.order + align_up((size_t)B * N * sizeof(int32_t), 256);
+    l.seg_hi = l.seg_lo + align_up((size_t)B * V * sizeof(int32_t), 256);
+    l.total = l.seg_hi + align_up((size_t)B * V * sizeof(int32_t), 256);
+    return l;
+}
+extern "C" size_t parrot_ctc_grad_workspace_bytes(int32_t B, int32_t T, int32_t V, int32_t N) {
+    if (B <= 0 || B > 65535 || T <= 0 || T > ALIGN_MAX_T || N <= 0 || N > ALIGN_MAX_N || V <= 0) return 0;
+    return ctc_grad_layout(B, T, V, N).total;
+}
+extern "C" int parrot_ctc_loss_grad(const float* logits, const int64_t* tokens, const int32_t* mel_len, const int32_t* tokens_len, int32_t B,
+                                    int32_t T, int32_t V, int32_t N, const double* row_weight, int32_t zero_infinity, double* nll_out,
+                                    float* grad_out, void* ws, size_t ws_bytes, void* stream) {
+    if (!logits || !tokens || !mel_len || !tokens_len || !nll_out || !grad_out || !ws) return fail(PARROT_E_INVALID, "ctc_loss_grad: null argument");
+    if (B <= 0 || B > 65535 || T <= 0 || N <= 0 || V <= 0) return fail(PARROT_E_INVALID, "ctc_loss_grad: need 1 <= B <= 65535 and T, N, V >= 1");
+    if (T > ALIGN_MAX_T || N > ALIGN_MAX_N) return fail(PARROT_E_UNSUPPORTED, "ctc_loss_grad: at most 32768 frames and 2048 tokens per utterance");
+    const CtcGradLayout l = ctc_grad_layout(B, T, V, N);
+    if (ws_bytes < l.total) return fail(PARROT_E_NOMEM, "ctc_loss_grad: workspace too small");
+    hipStream_t s = (hipStream_t)stream;
+    if (poison_word()) {
+        TRY(poison(ws, ws_bytes, s));
+        TRY(poison(nll_out, (size_t)B * sizeof(double), s));
+        TRY(poison(grad_out, (size_t)B * T * V * sizeof(float), s));
+    }
+    HIP_TRY(hipMemsetAsync(ws, 0, sizeof(int), s));
+    char* base = (char*)ws;
+    double* lse = (double*)(base + l.lse);
+    CtcGradWs g{(double*)(base + l.occ), (int32_t*)(base + l.order), (int32_t*)(base + l.seg_lo), (int32_t*)(base + l.seg_hi)};
+    HIP_TRY(launch_ctc_lse(logits, mel_len, lse, B, T, V, (int*)ws, s));
+    HIP_TRY(launch_ctc_alpha(logits, tokens, mel_len, tokens_len, lse, B, T, V, N, nll_out, nullptr, g.occ, (int*)ws, s));
+    HIP_TRY(launch_ctc_grad(logits, tokens, mel_len, tokens_len, lse, nll_out, row_weight, zero_infinity ? 1 : 0, B, T, V, N, g, grad_out, s));
     return PARROT_OK;
 }
 static int aligner_status(int h) {
