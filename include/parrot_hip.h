@@ -360,6 +360,28 @@ int parrot_mel_forward(parrot_mel_t*, const float* wav, int64_t row_stride, cons
 size_t parrot_mel_l1_workspace_bytes(int32_t B, int32_t n_mels, int32_t T);
 int parrot_mel_l1(const float* a, const float* b, const int32_t* n_frames /* nullable */, int32_t B, int32_t n_mels, int32_t T,
                   double* out_f64, float* mean_f32 /* nullable */, void* ws, size_t ws_bytes, void* stream);
+/* The training loss of the generator (utils/vocoder/train.py:157, F.l1_loss(y_mel, y_g_hat_mel), before the factor 45) and its
+ * gradient with respect to the waveform, in one stateless call that runs the forward itself:
+ *   loss = reduce |parrot_mel_forward(wav, n_samples) - target|,   grad_wav = scale * d loss / d wav        (B, N) fp32, dense rows
+ * target (B, n_mels, N / hop) fp32.  reduction PARROT_MEL_REDUCE_MEAN: loss (1 float) is parrot_mel_l1's mean_f32 of the two
+ * spectrograms with n_frames = n_samples / hop, bit for bit; PARROT_MEL_REDUCE_SUM: loss (1 double) is the row sums added in row
+ * order, every real element weighted 1, so that a row's gradient depends on that row alone.  out_f64 (2B doubles) as parrot_mel_l1.
+ * torch's autograd rules of dataset.py:55-67: d|x| = sgn(x) (0 at 0); the clamp passes the gradient where mel >= 1e-5 and 0 below;
+ * the magnitude's gradient re / mag, im / mag is finite at re = im = 0; the reflect pad's adjoint adds the mirrored contributions
+ * onto the interior samples, row b folding at its OWN end n_samples[b] - 1; grad_wav[b, n_samples[b]:] is exactly 0, frames at and
+ * beyond n_samples[b] / hop contribute nothing, and padded samples no frame reads get nothing.  No floating-point atomics: two
+ * calls agree bit for bit.
+ * Precision: the forward half is the handle's own; the two transposed GEMMs (basis^T, DFT^T) are plans of their own in
+ * PARROT_PREC_F32 for every handle (1 / mel reaches 5e4, beyond the fp16 split scheme's range), the DFT's summed in 8 channel
+ * groups as the f32 handle's forward DFT is; they run on unit-weight operands: scale / count is applied once, where grad_wav is
+ * written.  Status through parrot_mel_check / parrot_mel_status_async as the forward: 8 a short row, 5 a
+ * non-finite mel or gradient value. */
+#define PARROT_MEL_REDUCE_MEAN 0
+#define PARROT_MEL_REDUCE_SUM 1
+size_t parrot_mel_l1_grad_workspace_bytes(const parrot_mel_t*, int32_t B, int32_t N);
+int parrot_mel_l1_grad(parrot_mel_t*, const float* wav, int64_t row_stride, const int32_t* n_samples /* nullable */, const float* target,
+                       int32_t B, int32_t N, int32_t reduction, double scale, double* out_f64, void* loss, float* grad_wav, void* ws,
+                       size_t ws_bytes, void* stream);
 /* Synchronises `stream`, clears the flag: 0, PARROT_E_INVALID (status 8) or PARROT_E_NONFINITE (status 5). */
 int parrot_mel_check(parrot_mel_t*, void* stream);
 /* The same flag without a synchronisation: see parrot_voc_status_async. */

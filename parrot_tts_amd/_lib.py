@@ -140,6 +140,8 @@ SIGNATURES = {
     "parrot_mel_forward": (C.c_int, [vp, vp, C.c_int64, vp, i32, i32, vp, vp, sz, vp]),
     "parrot_mel_l1_workspace_bytes": (sz, [i32, i32, i32]),
     "parrot_mel_l1": (C.c_int, [vp, vp, vp, i32, i32, i32, vp, vp, vp, sz, vp]),
+    "parrot_mel_l1_grad_workspace_bytes": (sz, [vp, i32, i32]),
+    "parrot_mel_l1_grad": (C.c_int, [vp, vp, C.c_int64, vp, vp, i32, i32, i32, C.c_double, vp, vp, vp, vp, sz, vp]),
     "parrot_mel_check": (C.c_int, [vp, vp]),
     "parrot_mel_status_async": (C.c_int, [vp, vp, vp]),
     "parrot_aligner_create": (C.c_int, [C.POINTER(vp), C.POINTER(AlignerCfg), C.POINTER(AlignerWeights)]),

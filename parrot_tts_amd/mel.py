@@ -5,6 +5,8 @@ distance of two log-mel spectrograms (``F.l1_loss``, utils/vocoder/train.py:213)
     mel_spectrogram(y, n_fft, num_mels, sampling_rate, hop_size, win_size, fmin, fmax, center=False)   the reference's signature
     MelSpectrogram(h)(wav, n_samples=None)                                                             ragged batches
     mel_l1(a, b, n_frames=None) -> (batch mean, per-row means)
+    MelSpectrogram.l1_loss_and_grad(wav, target, n_samples=None, reduction="mean") -> (loss, d loss / d wav)
+    mel_l1_trainable(mel, wav, target, ...) / MelL1Loss(h)(y_g_hat, y_mel)                             the training loss (train.py:157)
 
 The library is handed the window (``torch.hann_window(win_size)``, fp32, as the reference builds it) and the mel basis
 (``slaney_mel_basis``); the framed DFT and the mel projection run on the conv kernels in a parity-grade precision (f16x3 by
@@ -17,6 +19,7 @@ from typing import Optional, Tuple
 
 import numpy as np
 import torch
+from torch import nn
 
 from . import _lib
 from .ops import PREC_NAMES, PREC_STR, dptr, require_cuda, stream_ptr
@@ -133,8 +136,8 @@ class MelSpectrogram:
         dev = torch.device("cuda", torch.cuda.current_device()) if dev.index is None else dev
         return PREC_STR[int(_lib.lib().parrot_mel_precision(self._handle(dev)))]
 
-    @torch.no_grad()
-    def __call__(self, wav: torch.Tensor, n_samples=None, check: bool = True) -> torch.Tensor:
+    def _args(self, wav: torch.Tensor, n_samples):
+        """-> (wav (B, N) fp32 with unit sample stride, n_samples (B) int32 on the device or None), validated."""
         require_cuda(wav, "wav")
         if wav.dim() == 3 and wav.shape[1] == 1:  # the generator's (B, 1, N)
             wav = wav[:, 0]
@@ -159,6 +162,13 @@ class MelSpectrogram:
             if not ns.is_cuda and B and (int(ns.min()) < 0 or int(ns.max()) > N):
                 raise ValueError(f"n_samples must lie in [0, {N}] (samples of a row of the padded batch), got {ns.tolist()}")
             ns = ns.to(dev, torch.int32).contiguous()
+        return wav, ns
+
+    @torch.no_grad()
+    def __call__(self, wav: torch.Tensor, n_samples=None, check: bool = True) -> torch.Tensor:
+        wav, ns = self._args(wav, n_samples)
+        dev = wav.device
+        B, N = wav.shape
         lib = _lib.lib()
         out = torch.empty((B, self.num_mels, N // self.hop_size), dtype=torch.float32, device=dev)
         with torch.cuda.device(dev):
@@ -169,9 +179,42 @@ class MelSpectrogram:
                 self.check(dev)
         return out
 
+    @torch.no_grad()
+    def l1_loss_and_grad(self, wav: torch.Tensor, target: torch.Tensor, n_samples=None, reduction: str = "mean") -> Tuple[torch.Tensor, torch.Tensor]:
+        """The generator's mel loss (train.py:157, ``F.l1_loss(y_mel, y_g_hat_mel)`` before the factor 45) and its gradient with
+        respect to the waveform in one device call: -> (loss, grad (B, N) fp32).  ``target`` (B, num_mels, N // hop_size) fp32.
+        "mean": ``loss`` is ``mel_l1(self(wav, n_samples), target, n_samples // hop_size)[0]`` bit for bit (0-dim fp32); "sum": the
+        sum of |a - b| over the real elements, every one weighted 1 (0-dim fp64), so that a row's gradient depends on that row
+        alone.  ``grad = d loss / d wav``: torch's autograd of dataset.py:55-67 (sgn with 0 at 0, the clamp passing where
+        mel >= 1e-5, the magnitude's gradient finite at 0, the reflect pad folding at each row's own end), exactly 0 at and beyond
+        ``n_samples[b]``.  No atomics on values: two calls agree bit for bit.  Raises as ``__call__`` (a short row, a non-finite
+        value: nothing is returned then)."""
+        if reduction not in ("mean", "sum"):
+            raise ValueError(f"l1_loss_and_grad: reduction must be 'mean' or 'sum', got {reduction!r}")
+        wav, ns = self._args(wav, n_samples)
+        require_cuda(target, "target")
+        dev = wav.device
+        B, N = wav.shape
+        want = (B, self.num_mels, N // self.hop_size)
+        if tuple(target.shape) != want:
+            raise ValueError(f"l1_loss_and_grad: target must be {want} (B, num_mels, N // hop_size), got {tuple(target.shape)}")
+        target = target.detach().to(dev, torch.float32).contiguous()
+        lib = _lib.lib()
+        mean = reduction == "mean"
+        out = torch.empty(2 * B, dtype=torch.float64, device=dev)
+        loss = torch.empty((), dtype=torch.float32 if mean else torch.float64, device=dev)
+        grad = torch.empty((B, N), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            h = self._handle(dev)
+            ws = torch.empty(max(int(lib.parrot_mel_l1_grad_workspace_bytes(h, B, N)), 1), dtype=torch.uint8, device=dev)
+            _lib.check(lib.parrot_mel_l1_grad(h, dptr(wav), wav.stride(0), dptr(ns), dptr(target), B, N, 0 if mean else 1, 1.0,
+                                              dptr(out), dptr(loss), dptr(grad), dptr(ws), ws.numel(), stream_ptr(dev)))
+            self.check(dev)
+        return loss, grad
+
     def check(self, device) -> None:
         """Synchronise and raise what the device flagged since the last check: a row no longer than the reflect pad
-        (the reference's F.pad raises), a non-finite mel value."""
+        (the reference's F.pad raises), a non-finite mel (or gradient) value."""
         dev = torch.device(device)
         with torch.cuda.device(dev):
             _lib.check(_lib.lib().parrot_mel_check(self._handle(dev), stream_ptr(dev)))
@@ -227,3 +270,57 @@ def mel_l1(a: torch.Tensor, b: torch.Tensor, n_frames=None) -> Tuple[torch.Tenso
         ws = torch.empty(max(int(lib.parrot_mel_l1_workspace_bytes(B, M, T)), 1), dtype=torch.uint8, device=dev)
         _lib.check(lib.parrot_mel_l1(dptr(a), dptr(b), dptr(nf), B, M, T, dptr(out), dptr(mean), dptr(ws), ws.numel(), stream_ptr(dev)))
     return mean, out[:B] / out[B:]
+
+
+class _MelL1Fn(torch.autograd.Function):
+    """With a waveform that requires a gradient the forward is ONE ``parrot_mel_l1_grad`` call whose unit-scale gradient is kept
+    for the backward (training always calls it: nothing is computed twice); otherwise the plain forward and ``mel_l1``.  Only the
+    waveform gets a gradient, and there is no double backward."""
+
+    @staticmethod
+    def forward(ctx, wav, mel, target, n_samples, reduction):
+        ctx.in_shape, ctx.in_dtype = wav.shape, wav.dtype
+        # ("sum" without a gradient to keep also takes the one call: its value is the fp64 row sums added in row order on the device,
+        # which mel_l1's per-row means do not give back bit for bit; the gradient written beside it is dropped)
+        if ctx.needs_input_grad[0] or reduction != "mean":
+            loss, grad = mel.l1_loss_and_grad(wav, target, n_samples, reduction)
+            if ctx.needs_input_grad[0]:
+                ctx.save_for_backward(grad)
+            return loss
+        n_frames = None if n_samples is None else torch.div(torch.as_tensor(n_samples), mel.hop_size, rounding_mode="floor")
+        return mel_l1(mel(wav, n_samples), target, n_frames)[0]
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_output):
+        (grad,) = ctx.saved_tensors
+        g = grad * grad_output.detach().to(grad.device, torch.float32)  # (a 0-dim grad_output broadcasts)
+        return g.reshape(ctx.in_shape).to(ctx.in_dtype), None, None, None, None
+
+
+def mel_l1_trainable(mel: MelSpectrogram, wav: torch.Tensor, target: torch.Tensor, n_samples=None, reduction: str = "mean") -> torch.Tensor:
+    """``mel_l1(mel(wav, n_samples), target, n_samples // hop)[0]`` as a differentiable function of ``wav`` ((B, N) or the
+    generator's (B, 1, N)): the same value ("mean" 0-dim fp32; "sum" 0-dim fp64), and ``.backward()`` hands on the gradient the
+    device computed with the loss -- deterministic, so it also runs under ``torch.use_deterministic_algorithms(True)``.
+    ``target`` gets no gradient.  No double backward."""
+    if reduction not in ("mean", "sum"):
+        raise ValueError(f"mel_l1_trainable: reduction must be 'mean' or 'sum', got {reduction!r}")
+    if isinstance(target, torch.Tensor) and target.requires_grad:
+        target = target.detach()
+    return _MelL1Fn.apply(wav, mel, target, n_samples, reduction)
+
+
+class MelL1Loss(nn.Module):
+    """The mel term of the generator loss for the reference trainer: utils/vocoder/train.py:151-157,
+    ``F.l1_loss(y_mel, mel_spectrogram(y_g_hat.squeeze(1), ..., h.fmax_for_loss)) * 45``, becomes ``MelL1Loss(h)(y_g_hat, y_mel) * 45``.
+    ``forward(y_g_hat (B, 1, N) or (B, N), y_mel (B, num_mels, N // hop_size), n_samples=None)``; ``h`` and the keywords as
+    ``MelSpectrogram``'s."""
+
+    def __init__(self, h=None, reduction: str = "mean", **kw) -> None:
+        super().__init__()
+        if reduction not in ("mean", "sum"):
+            raise ValueError(f"MelL1Loss: reduction must be 'mean' or 'sum', got {reduction!r}")
+        self.mel, self.reduction = MelSpectrogram(h, **kw), reduction
+
+    def forward(self, y_g_hat: torch.Tensor, y_mel: torch.Tensor, n_samples=None) -> torch.Tensor:
+        return mel_l1_trainable(self.mel, y_g_hat, y_mel, n_samples, self.reduction)
