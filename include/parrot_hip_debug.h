@@ -50,6 +50,18 @@ int parrot_voc_debug_absmax(parrot_voc_t*, float* dst_dev);
  * enc_ptrs[1 + n] = encoder block n, enc_ptrs[1 + enc_layers] = encoder output (+ speaker); dec_ptrs[0] = length
  * regulator output + pe[L], dec_ptrs[1 + n] = decoder block n.  Pass NULL, NULL to switch it off. */
 int parrot_tte_debug_stages(parrot_tte_t*, float* const* enc_ptrs, float* const* dec_ptrs);
+/* Tests: the TTE's attention cores and its LayerNorm on their own, through the very launch code of the FFT block (csrc/host_tte.hip).
+ * parrot_debug_attention: ctx (B, H hd, T) = softmax(q k^T sqrt(1 / hd) + key mask) v per (batch, head) of the channel-first
+ * projections qkv (B, 3, H hd, T); valid (B, T) u8, non-zero = attend to this key (a row without a valid key: NaN throughout, as
+ * torch).  core: 0 the three-kernel path (batched GEMM, masked softmax, batched GEMM over a (B, H, T, T) score tensor in ws; any
+ * hd and T), 1 the fused core (hd = 128 and T <= 256), 2 the flash core on the fp16 split pipe (hd in {16, 32, 64, 128}, any T).
+ * A core that does not take the shape: PARROT_E_UNSUPPORTED.  ws: parrot_debug_attention_workspace_bytes (never 0 for valid sizes).
+ * parrot_debug_layernorm: y = LayerNorm over the channels of x (B, C, T) (of relu(x) when relu_in), eps 1e-5, affine (C). */
+size_t parrot_debug_attention_workspace_bytes(int32_t B, int32_t T, int32_t H, int32_t core);
+int parrot_debug_attention(const float* qkv, const uint8_t* valid, float* ctx, int32_t B, int32_t T, int32_t H, int32_t hd, int32_t core,
+                           void* ws, size_t ws_bytes, void* stream);
+int parrot_debug_layernorm(const float* x, const float* gamma, const float* beta, float* y, int32_t B, int32_t C, int32_t T,
+                           int32_t relu_in, void* stream);
 /* Stage taps of the aligner: while set, every parrot_aligner_forward copies the activation after the third BatchNorm, channel-first
  * (B, conv_dim, T), to bn3_dev and the LSTM output (B, T, 2 lstm_dim) to lstm_dev (DEVICE buffers; NULL entries are skipped). */
 int parrot_aligner_debug_stages(parrot_aligner_t*, float* bn3_dev, float* lstm_dev);

@@ -129,6 +129,9 @@ SIGNATURES = {
     "parrot_tte_status_peek_async": (C.c_int, [vp, vp, vp]),
     "parrot_tte_guard_stats_async": (C.c_int, [vp, vp, vp]),
     "parrot_tte_debug_stages": (C.c_int, [vp, C.POINTER(vp), C.POINTER(vp)]),
+    "parrot_debug_attention_workspace_bytes": (sz, [i32, i32, i32, i32]),
+    "parrot_debug_attention": (C.c_int, [vp, vp, vp, i32, i32, i32, i32, i32, vp, sz, vp]),
+    "parrot_debug_layernorm": (C.c_int, [vp, vp, vp, vp, i32, i32, i32, i32, vp]),
     "parrot_length_regulator_workspace_bytes": (sz, [i32, i32, i32, i32]),
     "parrot_length_regulator": (C.c_int, [vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, sz, vp]),
     "parrot_mel_create": (C.c_int, [C.POINTER(vp), C.POINTER(MelCfg), c_float_p, c_float_p]),

@@ -252,6 +252,60 @@ static int layernorm(const float* x, const float* g, const float* b, float* y, i
     return PARROT_OK;
 }
 
+// The attention core softmax(q k^T sqrt(1/hd) + key mask) v of one FFT block on the channel-first (B, 3, D, T) projections:
+// ctx (B, D, T).  `core` names the launch sequence (fft_block picks it; parrot_debug_attention runs any of them on its own):
+//   ATTN_CORE_THREE  bgemm_mfma_kernel -> softmax_mask_kernel -> bgemm_mfma_kernel through scores (B, H, T, T): any hd, any T
+//   ATTN_CORE_FUSED  attn_fused_kernel<128, 32>, one launch: hd = 128 and T <= ATTN_TMAX only
+//   ATTN_CORE_FLASH  attn_flash_kernel<hd>, online softmax on the fp16 split pipe: attn_flash_has(hd), any T
+// The caller has checked that the core takes the shape; scores is only read by ATTN_CORE_THREE.
+enum { ATTN_CORE_THREE = 0, ATTN_CORE_FUSED = 1, ATTN_CORE_FLASH = 2 };
+static int attention_core(int core, const float* qkv, const uint8_t* valid, float* ctx, float* scores, int B, int T, int H, int D,
+                          hipStream_t s) {
+    const int hd = D / H;
+    const long DT = (long)D * T;
+    if (core == ATTN_CORE_FLASH) {  // any T, online softmax, no score tensor (attn.h: attn_flash_kernel)
+        AttnParams p{};
+        p.qkv = qkv; p.valid = valid; p.ctx = ctx;
+        p.T = T; p.H = H; p.D = D; p.hd = hd;
+        p.alpha = (float)std::sqrt(1.0 / (double)hd);
+        HIP_TRY(launch_attn_flash(p, B, s));
+    } else if (core == ATTN_CORE_FUSED) {  // scores, softmax and context in one launch (attn.h)
+        AttnParams p{};
+        p.qkv = qkv; p.valid = valid; p.ctx = ctx;
+        p.T = T; p.H = H; p.D = D; p.hd = hd;
+        p.alpha = (float)std::sqrt(1.0 / (double)hd);
+        const size_t lds = (size_t)32 * (((T + 31) / 32) * 32 + 1) * sizeof(float);  // 32-query tiles (33 KiB at T = 256: no opt-in needed)
+        hipLaunchKernelGGL((attn_fused_kernel<128, 32>), dim3((T + 31) / 32, B * H), dim3(256), lds, s, p);
+        HIP_TRY(hipGetLastError());
+    } else {
+    {   // scores[b,h][tq][tk] = sum_c (q[c][tq] * sqrt(1/hd)) * k[c][tk]
+        BgemmParams p{};
+        p.A = qkv; p.B = qkv + DT; p.C = scores;
+        p.M = T; p.N = T; p.K = hd;
+        p.a_sk = T; p.a_sm = 1; p.b_sk = T; p.b_sn = 1;
+        p.a_zb = 3 * DT; p.a_zh = (long)hd * T; p.b_zb = 3 * DT; p.b_zh = (long)hd * T;
+        p.c_zb = (long)H * T * T; p.c_zh = (long)T * T; p.ldc = T; p.H = H;
+        p.alpha = (float)std::sqrt(1.0 / (double)hd);
+        hipLaunchKernelGGL(bgemm_mfma_kernel, dim3((T + 63) / 64, (T + 63) / 64, B * H), dim3(256), 0, s, p);
+        HIP_TRY(hipGetLastError());
+    }
+    hipLaunchKernelGGL(softmax_mask_kernel, dim3((B * H * T + 3) / 4), dim3(256), 0, s, scores, valid, B * H * T, T, H * T);
+    HIP_TRY(hipGetLastError());
+    {   // ctx[b][h*hd + c][tq] = sum_tk v[c][tk] * P[tq][tk]
+        BgemmParams p{};
+        p.A = qkv + 2 * DT; p.B = scores; p.C = ctx;
+        p.M = hd; p.N = T; p.K = T;
+        p.a_sk = 1; p.a_sm = T; p.b_sk = 1; p.b_sn = T;
+        p.a_zb = 3 * DT; p.a_zh = (long)hd * T; p.b_zb = (long)H * T * T; p.b_zh = (long)T * T;
+        p.c_zb = DT; p.c_zh = (long)hd * T; p.ldc = T; p.H = H;
+        p.alpha = 1.0f;
+        hipLaunchKernelGGL(bgemm_mfma_kernel, dim3((T + 63) / 64, (hd + 63) / 64, B * H), dim3(256), 0, s, p);
+        HIP_TRY(hipGetLastError());
+    }
+    }
+    return PARROT_OK;
+}
+
 // FFTBlock.forward (fft.py:94-100): x -> out (may alias x).  valid (B,T) u8: 1 = attend to this key.
 // row_len (B) i32 device, nullable: ROW-EXACT mode -- row b holds row_len[b] real positions and every conv applies its zero padding
 // at the row's own end (the reference run of that utterance alone, fft.py:78-82); NULL: the reference's padded-batch semantics, pad
@@ -266,47 +320,10 @@ static int fft_block(const parrot_tte* t, const FftLayer* L, TteScratch& w, floa
         TRY(conv_launch(L->qkv.get(), w.n, nullptr, w.qkv1, B, T, EPI_STORE, 1.f, s));
         TRY(conv_launch(L->in_proj.get(), w.qkv1, nullptr, w.qkv2, B, T, EPI_STORE, 1.f, s));
     }
-    const long DT = (long)D * T;
-    if (t->flash) {  // any T, online softmax, no score tensor (attn.h: attn_flash_kernel)
-        AttnParams p{};
-        p.qkv = w.qkv2; p.valid = valid; p.ctx = w.ctx;
-        p.T = T; p.H = H; p.D = D; p.hd = hd;
-        p.alpha = (float)std::sqrt(1.0 / (double)hd);
-        HIP_TRY(launch_attn_flash(p, B, s));
-    } else if (T <= ATTN_TMAX && hd == 128) {  // scores, softmax and context in one launch (attn.h)
-        AttnParams p{};
-        p.qkv = w.qkv2; p.valid = valid; p.ctx = w.ctx;
-        p.T = T; p.H = H; p.D = D; p.hd = hd;
-        p.alpha = (float)std::sqrt(1.0 / (double)hd);
-        const size_t lds = (size_t)32 * (((T + 31) / 32) * 32 + 1) * sizeof(float);  // 32-query tiles (33 KiB at T = 256: no opt-in needed)
-        hipLaunchKernelGGL((attn_fused_kernel<128, 32>), dim3((T + 31) / 32, B * H), dim3(256), lds, s, p);
-        HIP_TRY(hipGetLastError());
-    } else {
-    {   // scores[b,h][tq][tk] = sum_c (q[c][tq] * sqrt(1/hd)) * k[c][tk]
-        BgemmParams p{};
-        p.A = w.qkv2; p.B = w.qkv2 + DT; p.C = w.scores;
-        p.M = T; p.N = T; p.K = hd;
-        p.a_sk = T; p.a_sm = 1; p.b_sk = T; p.b_sn = 1;
-        p.a_zb = 3 * DT; p.a_zh = (long)hd * T; p.b_zb = 3 * DT; p.b_zh = (long)hd * T;
-        p.c_zb = (long)H * T * T; p.c_zh = (long)T * T; p.ldc = T; p.H = H;
-        p.alpha = (float)std::sqrt(1.0 / (double)hd);
-        hipLaunchKernelGGL(bgemm_mfma_kernel, dim3((T + 63) / 64, (T + 63) / 64, B * H), dim3(256), 0, s, p);
-        HIP_TRY(hipGetLastError());
-    }
-    hipLaunchKernelGGL(softmax_mask_kernel, dim3((B * H * T + 3) / 4), dim3(256), 0, s, w.scores, valid, B * H * T, T, H * T);
-    HIP_TRY(hipGetLastError());
-    {   // ctx[b][h*hd + c][tq] = sum_tk v[c][tk] * P[tq][tk]
-        BgemmParams p{};
-        p.A = w.qkv2 + 2 * DT; p.B = w.scores; p.C = w.ctx;
-        p.M = hd; p.N = T; p.K = T;
-        p.a_sk = 1; p.a_sm = T; p.b_sk = 1; p.b_sn = T;
-        p.a_zb = 3 * DT; p.a_zh = (long)hd * T; p.b_zb = (long)H * T * T; p.b_zh = (long)T * T;
-        p.c_zb = DT; p.c_zh = (long)hd * T; p.ldc = T; p.H = H;
-        p.alpha = 1.0f;
-        hipLaunchKernelGGL(bgemm_mfma_kernel, dim3((T + 63) / 64, (hd + 63) / 64, B * H), dim3(256), 0, s, p);
-        HIP_TRY(hipGetLastError());
-    }
-    }
+    // the selection rule: a flash handle takes attn_flash_kernel at any T; the fp32-MFMA handles take the fused core where it
+    // fits (hd = 128, T <= 256) and the three-kernel path everywhere else
+    const int core = t->flash ? ATTN_CORE_FLASH : (T <= ATTN_TMAX && hd == 128) ? ATTN_CORE_FUSED : ATTN_CORE_THREE;
+    TRY(attention_core(core, w.qkv2, valid, w.ctx, w.scores, B, T, H, D, s));
     if (L->merged) {
         TRY(conv_launch(L->wo.get(), w.ctx, x, w.h, B, T, EPI_STORE, 1.f, s));        // h = x + attn
     } else {
@@ -533,6 +550,50 @@ extern "C" int parrot_tte_loss(const float* logits, const int64_t* targets, int3
     hipLaunchKernelGGL(loss_reduce_kernel, dim3(1), dim3(LOSS_REDUCE), 0, s, nll, cnt, bad, nblk, log_dur, dur, src_mask, n_src, out, losses);
     HIP_TRY(hipGetLastError());
     return PARROT_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// The attention cores and the LayerNorm on their own (tests: include/parrot_hip_debug.h).  Both run the functions fft_block runs.
+// ---------------------------------------------------------------------------------------------
+static float* debug_attention_ws(Arena& a, int B, int T, int H, int core) {
+    float* scores = core == ATTN_CORE_THREE ? a.take<float>((size_t)B * H * T * T) : nullptr;
+    a.take<char>(1);  // (never empty: the fused and flash cores take no workspace, and the entry refuses a null one)
+    return scores;
+}
+extern "C" size_t parrot_debug_attention_workspace_bytes(int32_t B, int32_t T, int32_t H, int32_t core) {
+    if (B <= 0 || T <= 0 || H <= 0 || core < ATTN_CORE_THREE || core > ATTN_CORE_FLASH) return 0;
+    Arena a(nullptr, 0);
+    (void)debug_attention_ws(a, B, T, H, core);
+    return align_up(a.off, 256);
+}
+extern "C" int parrot_debug_attention(const float* qkv, const uint8_t* valid, float* ctx, int32_t B, int32_t T, int32_t H, int32_t hd,
+                                      int32_t core, void* ws, size_t ws_bytes, void* stream) {
+    if (!qkv || !valid || !ctx || !ws) return fail(PARROT_E_INVALID, "debug_attention: null argument");
+    if (B <= 0 || T <= 0 || H <= 0 || hd <= 0) return fail(PARROT_E_INVALID, "debug_attention: non-positive size");
+    if (core < ATTN_CORE_THREE || core > ATTN_CORE_FLASH) return fail(PARROT_E_INVALID, "debug_attention: core in 0 .. 2");
+    if ((long)B * H > 65535 || (long)B * H * T >= (1L << 30) || (long)H * hd >= (1L << 30))  // (grid rows; softmax_mask_kernel's int row count)
+        return fail(PARROT_E_UNSUPPORTED, "debug_attention: B H > 65535, or B H T / H hd beyond the kernels' 32-bit indices");
+    if (core == ATTN_CORE_FUSED && (hd != 128 || T > ATTN_TMAX))
+        return fail(PARROT_E_UNSUPPORTED, "debug_attention: the fused core takes hd = 128 and T <= 256 only");
+    if (core == ATTN_CORE_FLASH && !attn_flash_has(hd)) return fail(PARROT_E_UNSUPPORTED, "debug_attention: the flash core takes hd in {16, 32, 64, 128} only");
+    hipStream_t s = (hipStream_t)stream;
+    Arena a(ws, ws_bytes);
+    float* scores = debug_attention_ws(a, B, T, H, core);
+    if (!a.ok) return fail(PARROT_E_NOMEM, "debug_attention: workspace too small");
+    if (poison_word()) {
+        TRY(poison(ws, ws_bytes, s));
+        TRY(poison(ctx, (size_t)B * H * hd * T * sizeof(float), s));
+    }
+    return attention_core(core, qkv, valid, ctx, scores, B, T, H, H * hd, s);
+}
+extern "C" int parrot_debug_layernorm(const float* x, const float* gamma, const float* beta, float* y, int32_t B, int32_t C, int32_t T,
+                                      int32_t relu_in, void* stream) {
+    if (!x || !gamma || !beta || !y) return fail(PARROT_E_INVALID, "debug_layernorm: null argument");
+    if (B <= 0 || C <= 0 || T <= 0) return fail(PARROT_E_INVALID, "debug_layernorm: non-positive size");
+    if (B > 65535) return fail(PARROT_E_UNSUPPORTED, "debug_layernorm: B > 65535 (one grid row per batch row)");
+    hipStream_t s = (hipStream_t)stream;
+    if (poison_word()) TRY(poison(y, (size_t)B * C * T * sizeof(float), s));
+    return layernorm(x, gamma, beta, y, B, C, T, relu_in != 0, s);
 }
 
 extern "C" int parrot_tte_debug_stages(parrot_tte_t* t, float* const* enc_ptrs, float* const* dec_ptrs) {

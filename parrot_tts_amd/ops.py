@@ -1,4 +1,5 @@
-"""Thin tensor-level wrappers over the single-op C-ABI entry points (conv plan, int16 cast, selftest).
+"""Thin tensor-level wrappers over the single-op C-ABI entry points (conv plan, int16 cast, selftest, the TTE's attention cores
+and LayerNorm on their own).
 
 PyTorch is plumbing only: it owns device memory and the stream; all arithmetic happens in
 libparrot_hip.so."""
@@ -160,3 +161,44 @@ def length_regulator(seq: torch.Tensor, dur: torch.Tensor):
         _lib.check(lib.parrot_length_regulator(dptr(seq), dptr(dur), B, S, D, L, dptr(out), dptr(mask), dptr(lens), dptr(ws), ws.numel(),
                                                stream_ptr(seq.device)))
     return out, mask.bool(), lens.cpu().tolist()
+
+
+ATTN_THREE_KERNEL, ATTN_FUSED, ATTN_FLASH = 0, 1, 2
+
+
+def debug_attention(qkv: torch.Tensor, valid: torch.Tensor, heads: int, core: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """One attention core of the TTE's FFT block on its own (tests; include/parrot_hip_debug.h): qkv (B, 3, D, T) f32 channel-first,
+    valid (B, T) uint8 with non-zero = attend to this key -> ctx (B, D, T).  ``core``: ATTN_THREE_KERNEL, ATTN_FUSED or ATTN_FLASH;
+    a core that does not take (D / heads, T) raises ParrotHipError with code -5."""
+    require_cuda(qkv, "qkv")
+    assert qkv.dtype == torch.float32 and qkv.is_contiguous() and qkv.dim() == 4 and qkv.shape[1] == 3
+    B, _, D, T = qkv.shape
+    assert D % heads == 0 and valid.dtype == torch.uint8 and valid.is_contiguous() and tuple(valid.shape) == (B, T)
+    require_cuda(valid, "valid")
+    if out is None:
+        out = torch.empty((B, D, T), device=qkv.device, dtype=torch.float32)
+    assert out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (B, D, T)
+    lib = _lib.lib()
+    ws = torch.empty(lib.parrot_debug_attention_workspace_bytes(B, T, heads, int(core)), dtype=torch.uint8, device=qkv.device)
+    with torch.cuda.device(qkv.device):
+        _lib.check(lib.parrot_debug_attention(dptr(qkv), dptr(valid), dptr(out), B, T, heads, D // heads, int(core), dptr(ws), ws.numel(),
+                                              stream_ptr(qkv.device)))
+    return out
+
+
+def debug_layernorm(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, relu_in: bool = False,
+                    out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The TTE's LayerNorm over the channels of a channel-first (B, C, T) f32 tensor (of relu(x) when ``relu_in``), eps 1e-5, on its
+    own (tests; include/parrot_hip_debug.h)."""
+    require_cuda(x, "x")
+    assert x.dtype == torch.float32 and x.is_contiguous() and x.dim() == 3
+    B, C_, T = x.shape
+    for t in (gamma, beta):
+        assert t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == (C_,) and t.device == x.device
+    if out is None:
+        out = torch.empty_like(x)
+    assert out.dtype == torch.float32 and out.is_contiguous() and out.shape == x.shape
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.lib().parrot_debug_layernorm(dptr(x), dptr(gamma), dptr(beta), dptr(out), B, C_, T, int(bool(relu_in)),
+                                                     stream_ptr(x.device)))
+    return out

@@ -1,0 +1,373 @@
+"""GPU: the TTE's three attention cores and its LayerNorm on their own (parrot_debug_attention / parrot_debug_layernorm: the launch
+code of the FFT block itself, csrc/host_tte.hip attention_core() / layernorm()), element-wise against fp64.
+
+Attention.  The yardstick is the torch MHA math path in plain torch on the CPU in fp64, on the channel-first (B, 3, D, T) layout:
+q * sqrt(1 / hd), q k^T, masked_fill(-inf) over the masked keys, softmax, . v.  The same formula in fp32 on the CPU gives e32.
+    e = max|ctx - ref64| / max(1, max|ref64|)      over the batch rows that have a valid key
+Inputs are seeded randn with q scaled by s in {1, 8, 30}: the softmax goes from flat to nearly one-hot (scores of +-100 at s = 30).
+  * s in {1, 8}, every core: e <= 2e-5 (the project's single-layer bound) and e <= 4 e32 + 1e-6 (the criterion of
+    test_conv1d_split_schemes_match_fp64 with the CPU fp32 evaluation in the exact kernel's place).
+  * s = 30: e32 itself reaches 1.3e-5, so only the relative bound: cores 0 and 1 e <= 4 e32 + 1e-6; the flash core (fp16x3 products
+    drop a term of relative size 2^-22 against fp32's 2^-24 rounding) e <= FLASH_S30_FACTOR e32 + 1e-6, FLASH_S30_FACTOR = 4 = twice the
+    largest e / e32 measured on an MI355X over the 144 s = 30 calls below, rounded up: 1.96 (e = 1.7e-6; 1.55 over the calls with
+    e32 >= 1e-6, at hd 16, T 31; the largest e there 9.1e-6 where e32 is 8.4e-6).  The figures per core and s: DESIGN.md section 4.
+The shapes are the smallest that touch every boundary of each core (key tile of 32, wave of 32 queries, workgroup of 128 queries,
+odd and even tile counts, a last wave without a real query; K and M / N off the GEMM tiles on the three-kernel path); B = 3 and
+H in {1, 2, 3} so a wrong batch or head offset shows; eight key masks, three per call, one per batch row.
+
+LayerNorm.  F.layer_norm over the channel axis in fp64 (of relu(x) when relu_in): max|y - ref64| <= 2e-5 max(1, max|ref64|), on
+both sides of the kernel's C = 256 registers / global re-read threshold.
+
+The whole file also passes under PARROT_POISON_WS=nan (workspace and outputs filled with NaN at the top of the entry points)."""
+import functools
+import json
+import math
+import os
+import subprocess
+import sys
+
+import pytest
+import torch
+import torch.nn.functional as F
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+from parrot_tts_amd import _lib, ops  # noqa: E402
+from test_gpu_parity import _report  # noqa: E402  (the suite's parity report: measured errors, summarised in DESIGN.md)
+
+DEV = "cuda:0"
+THREE, FUSED, FLASH = ops.ATTN_THREE_KERNEL, ops.ATTN_FUSED, ops.ATTN_FLASH
+B = 3
+SCALES = (1.0, 8.0, 30.0)
+FLASH_S30_FACTOR = 4  # (2 x the measured 1.96, rounded up: the module docstring)
+
+SHAPES = {
+    FLASH: ([16, 32, 64, 128], [1, 31, 32, 33, 64, 65, 96, 127, 128, 129, 161, 257]),
+    FUSED: ([128], [1, 15, 16, 17, 31, 32, 33, 63, 65, 255, 256]),
+    THREE: ([8, 24, 33, 48, 128, 160], [1, 31, 33, 63, 64, 65, 129, 257]),
+}
+CASES = [(core, hd, T) for core, (hds, Ts) in SHAPES.items() for hd in hds for T in Ts]
+# the shapes of the bit-for-bit properties: every kernel template, one and several key tiles / query blocks / GEMM tiles
+FEW = [(FLASH, hd, T) for hd in (16, 32, 64, 128) for T in (33, 129, 257)] + [(FUSED, 128, T) for T in (17, 255, 256)] + \
+      [(THREE, hd, T) for hd in (24, 33, 160) for T in (33, 65, 257)]
+
+
+def _heads(T):
+    return 1 + T % 3
+
+
+# ---- key masks ---------------------------------------------------------------------------------------------------------------------
+def _mask(name, T):
+    m = torch.ones(T, dtype=torch.uint8)
+    if name == "prefix_half":
+        m[max(1, T // 2):] = 0
+    elif name == "prefix_1":
+        m[1:] = 0
+    elif name == "lead_hole":        # flash core: a key tile without a valid key BEFORE the first valid one
+        m[:min(32, T - 1)] = 0
+    elif name == "mid_hole":         # flash core: a key tile without a valid key after a valid one (T >= 96; else the full mask)
+        if T >= 96:
+            m[32:64] = 0
+    elif name == "alternate":
+        m[1::2] = 0
+    elif name == "last_only":
+        m[:T - 1] = 0
+    elif name == "bytes_255":        # any non-zero byte is a valid key
+        m[1::3] = 0
+        m *= 255
+    else:
+        assert name == "full"
+    return m
+
+
+MASK_GROUPS = [("full", "prefix_half", "prefix_1"), ("lead_hole", "mid_hole", "alternate"), ("last_only", "bytes_255", "full")]
+
+
+def _masks(names, T):
+    return torch.stack([_mask(n, T) for n in names])
+
+
+# ---- inputs and the CPU references (computed once per case, shared, never written) ----------------------------------------------------
+@functools.lru_cache(maxsize=32)
+def _qkv(hd, H, T, s, ramp=None):
+    """(B, 3, H hd, T) randn with q scaled by s.  ramp = "rise" / "fall": channel 0 of every head carries 0.5 (key index / 32) into
+    the score (q constant sqrt(hd), so alpha q = 1; k a ramp over the keys), rising or falling along the keys."""
+    gen = torch.Generator().manual_seed(1000003 * hd + 1009 * H + T)
+    x = torch.randn((B, 3, H * hd, T), generator=gen)
+    x[:, 0] *= s
+    if ramp:
+        t = torch.arange(T, dtype=torch.float32)
+        r = 0.5 * (t if ramp == "rise" else (T - 1 - t)) / 32.0
+        x[:, 0, 0::hd, :] = math.sqrt(hd)
+        x[:, 1, 0::hd, :] = r
+    return x
+
+
+def _mha(qkv, valid, H, dtype):
+    Bq, _, D, T = qkv.shape
+    hd = D // H
+    x = qkv.to(dtype).reshape(Bq, 3, H, hd, T)
+    q = x[:, 0] * math.sqrt(1.0 / hd)
+    s = q.transpose(-1, -2) @ x[:, 1]                                   # (B, H, Tq, Tk)
+    s = s.masked_fill(valid[:, None, None, :] == 0, float("-inf"))
+    p = torch.softmax(s, dim=-1)
+    return (x[:, 2] @ p.transpose(-1, -2)).reshape(Bq, D, T)            # (B, H, hd, Tq)
+
+
+@functools.lru_cache(maxsize=32)
+def _reference(hd, H, T, s, names, ramp=None):
+    qkv, valid = _qkv(hd, H, T, s, ramp), _masks(names, T)
+    ref = _mha(qkv, valid, H, torch.float64)
+    assert bool(torch.isfinite(ref).all())
+    scale = max(1.0, float(ref.abs().max()))
+    e32 = float((_mha(qkv, valid, H, torch.float32).double() - ref).abs().max()) / scale
+    return qkv, valid, ref, scale, e32
+
+
+def _run(core, qkv, valid, H, **kw):
+    return ops.debug_attention(qkv.to(DEV), valid.to(DEV), H, core, **kw).cpu()
+
+
+def _same(a, b):
+    """torch.equal with NaN == NaN."""
+    return torch.equal(torch.isnan(a), torch.isnan(b)) and torch.equal(torch.nan_to_num(a), torch.nan_to_num(b))
+
+
+def _check_accuracy(core, hd, T, s, names, ramp=None):
+    H = _heads(T)
+    qkv, valid, ref, scale, e32 = _reference(hd, H, T, s, names, ramp)
+    e = float((_run(core, qkv, valid, H).double() - ref).abs().max()) / scale
+    row = dict(core=core, hd=hd, T=T, H=H, s=s, masks="/".join(names), ramp=ramp, e=e, e32=e32, ratio=e / e32 if e32 > 0 else None)
+    print(json.dumps(row))
+    if s <= 8:
+        assert e <= 2e-5, row
+        assert e <= 4 * e32 + 1e-6, row
+    elif core != FLASH:
+        assert e <= 4 * e32 + 1e-6, row
+    else:
+        assert e <= FLASH_S30_FACTOR * e32 + 1e-6, row
+    return row
+
+
+def _worst(rows):
+    out = {}
+    for s in SCALES:
+        rs = [r for r in rows if r["s"] == s]
+        if rs:
+            w = max(rs, key=lambda r: r["e"])
+            ratios = [r["ratio"] for r in rs if r["e32"] >= 1e-6]
+            out["s%g" % s] = dict(e=w["e"], e32_there=w["e32"], e32_max=max(r["e32"] for r in rs),
+                                  ratio_max_where_e32_ge_1e6=max(ratios) if ratios else None)
+    return out
+
+
+@pytest.mark.parametrize("core,hd,T", CASES)
+def test_attention_core_vs_fp64(core, hd, T):
+    """Every core at every boundary shape, every mask, flat to one-hot softmax."""
+    rows = []
+    try:
+        for s in SCALES:
+            for names in MASK_GROUPS:
+                rows.append(_check_accuracy(core, hd, T, s, names))
+    finally:
+        _report(test="attention_core_vs_fp64", core=core, hd=hd, T=T, H=_heads(T), **_worst(rows))
+
+
+@pytest.mark.parametrize("core,hd,T", [c for c in CASES if c[2] >= 33])
+def test_running_maximum_rises_or_falls_on_every_key_tile(core, hd, T):
+    """One channel adds 0.5 (key / 32) to the score.  With the random part small (s = 0.05) the ramp decides the maximum: rising,
+    every key tile of the flash core raises every query's running maximum (the rescale of O on each tile); falling, no tile after
+    the first does.  s = 1 mixes the two within a wave.  Masks with holes as well: a tile that contributes nothing in between."""
+    rows = []
+    try:
+        for ramp in ("rise", "fall"):
+            for s in (0.05, 1.0):
+                for names in MASK_GROUPS[:2]:
+                    rows.append(_check_accuracy(core, hd, T, s, names, ramp))
+    finally:
+        w = max(rows, key=lambda r: r["e"]) if rows else {}
+        _report(test="attention_running_maximum", core=core, hd=hd, T=T, H=_heads(T), e=w.get("e"), e32=w.get("e32"), ramp=w.get("ramp"))
+
+
+@pytest.mark.parametrize("T", SHAPES[FUSED][1])
+def test_fused_core_is_bit_identical_to_the_three_kernel_path(T):
+    """csrc/attn.h: the fused core does the three-kernel path's arithmetic in its order.  Held to it, NaN rows included."""
+    H = _heads(T)
+    for s in SCALES:
+        for names in MASK_GROUPS:
+            qkv, valid = _qkv(128, H, T, s), _masks(names, T)
+            assert torch.equal(_run(FUSED, qkv, valid, H), _run(THREE, qkv, valid, H)), (T, s, names)
+    valid = _masks(MASK_GROUPS[1], T).clone()
+    valid[1] = 0
+    a, b = _run(FUSED, qkv, valid, H), _run(THREE, qkv, valid, H)
+    assert bool(torch.isnan(a[1]).all()) and _same(a, b)
+
+
+@pytest.mark.parametrize("core,hd,T", FEW)
+def test_row_without_a_valid_key_is_nan_and_alone(core, hd, T):
+    """As torch: softmax over nothing is NaN, in that batch row's whole ctx; the call's other rows do not notice."""
+    H = _heads(T)
+    qkv = _qkv(hd, H, T, 1.0)
+    for bad in range(B):
+        valid = _masks(MASK_GROUPS[1], T).clone()
+        full = valid.clone()
+        valid[bad] = 0
+        full[bad] = 1
+        got, base = _run(core, qkv, valid, H), _run(core, qkv, full, H)
+        others = [b for b in range(B) if b != bad]
+        assert bool(torch.isnan(got[bad]).all())
+        assert bool(torch.isfinite(base).all()) and torch.equal(got[others], base[others])
+
+
+@pytest.mark.parametrize("core,hd,T", FEW)
+def test_masked_keys_do_not_reach_the_result(core, hd, T):
+    """k and v at the masked keys replaced by other finite values of magnitude up to 1e3 (8 x stays inside fp16): their
+    probabilities are exact zeros, so ctx is bit-identical at EVERY query.  With q replaced there as well, the queries at those
+    positions are other queries; every query whose own q was left alone is still bit-identical."""
+    H = _heads(T)
+    qkv = _qkv(hd, H, T, 1.0)
+    gen = torch.Generator().manual_seed(7 * T + hd)
+    junk = (torch.rand(qkv.shape, generator=gen) * 2 - 1) * 1e3
+    for names in (("lead_hole", "mid_hole", "alternate"), ("prefix_half", "bytes_255", "last_only")):
+        valid = _masks(names, T)
+        masked = (valid == 0)[:, None, None, :].expand_as(qkv)
+        base = _run(core, qkv, valid, H)
+        kv_only = masked.clone()
+        kv_only[:, 0] = False
+        assert torch.equal(_run(core, torch.where(kv_only, junk, qkv), valid, H), base), names
+        got = _run(core, torch.where(masked, junk, qkv), valid, H)
+        keep = (valid != 0)[:, None, :].expand_as(base)
+        assert torch.equal(got[keep], base[keep]), names
+
+
+@pytest.mark.parametrize("core,hd,T", FEW)
+def test_rows_and_heads_are_independent_and_calls_repeat(core, hd, T):
+    names = MASK_GROUPS[1]
+    qkv, valid = _qkv(hd, 3, T, 8.0), _masks(names, T)
+    whole = _run(core, qkv, valid, 3)
+    assert torch.equal(_run(core, qkv, valid, 3), whole)                      # the same call again
+    for b in range(B):                                                        # row b alone
+        assert torch.equal(_run(core, qkv[b:b + 1].contiguous(), valid[b:b + 1].contiguous(), 3)[0], whole[b]), b
+    for h in range(3):                                                        # head h alone
+        sl = slice(h * hd, (h + 1) * hd)
+        assert torch.equal(_run(core, qkv[:, :, sl].contiguous(), valid, 1), whole[:, sl]), h
+
+
+GUARD, SENTINEL = 4096, 12345.0
+
+
+def _guarded(shape):
+    n = math.prod(shape)
+    buf = torch.full((GUARD + n + GUARD,), SENTINEL, device=DEV)
+    return buf, buf[GUARD:GUARD + n].view(shape)
+
+
+def _guards_intact(buf):
+    return bool((buf[:GUARD] == SENTINEL).all()) and bool((buf[-GUARD:] == SENTINEL).all())
+
+
+@pytest.mark.parametrize("core,hd,T", FEW + [(FLASH, 16, 1), (FUSED, 128, 1), (THREE, 8, 1)])
+def test_nothing_outside_ctx_is_written(core, hd, T):
+    H = _heads(T)
+    qkv, valid, ref, scale, _ = _reference(hd, H, T, 1.0, MASK_GROUPS[1])
+    buf, ctx = _guarded((B, H * hd, T))
+    got = _run(core, qkv, valid, H, out=ctx)
+    assert _guards_intact(buf)
+    assert float((got.double() - ref).abs().max()) / scale <= 2e-5
+
+
+def test_refusals():
+    lib = _lib.lib()
+    nb = lib.parrot_debug_attention_workspace_bytes
+
+    def call(core, hd, T, H=2, Bc=B, ws_bytes=None, null=None):
+        qkv = torch.zeros((max(Bc, 1), 3, H * hd, T), device=DEV)
+        valid = torch.ones((max(Bc, 1), T), dtype=torch.uint8, device=DEV)
+        ctx = torch.empty((max(Bc, 1), H * hd, T), device=DEV)
+        ws = torch.empty(max(nb(B, T, H, THREE), 256), dtype=torch.uint8, device=DEV)
+        ptr = {n: ops.dptr(None if n == null else t) for n, t in dict(qkv=qkv, valid=valid, ctx=ctx, ws=ws).items()}
+        r = lib.parrot_debug_attention(ptr["qkv"], ptr["valid"], ptr["ctx"], Bc, T, H, hd, core, ptr["ws"],
+                                       ws.numel() if ws_bytes is None else ws_bytes, ops.stream_ptr())
+        torch.cuda.synchronize()
+        return r
+
+    # a core that does not take the shape: PARROT_E_UNSUPPORTED, with a message
+    for core, hd, T in [(FUSED, 64, 32), (FUSED, 160, 32), (FUSED, 128, 257)] + [(FLASH, hd, 33) for hd in (8, 24, 33, 48, 160)]:
+        assert call(core, hd, T) == -5, (core, hd, T)
+        assert b"debug_attention" in lib.parrot_last_error()
+    with pytest.raises(_lib.ParrotHipError) as e:
+        ops.debug_attention(torch.zeros((1, 3, 48, 8), device=DEV), torch.ones((1, 8), dtype=torch.uint8, device=DEV), 2, FLASH)
+    assert e.value.code == -5
+    # ... and what each core does take at those edges
+    assert call(FUSED, 128, 256) == 0 and call(THREE, 128, 257) == 0 and call(THREE, 33, 33) == 0 and call(FLASH, 32, 257) == 0
+    # null pointers, non-positive sizes, a core that does not exist: PARROT_E_INVALID
+    for null in ("qkv", "valid", "ctx", "ws"):
+        assert call(THREE, 16, 8, null=null) == -1, null
+    assert call(THREE, 16, 8, Bc=0) == -1 and call(THREE, 0, 8) == -1 and call(3, 16, 8) == -1 and call(-1, 16, 8) == -1
+    assert nb(0, 8, 2, THREE) == 0 and nb(B, 0, 2, THREE) == 0 and nb(B, 8, 0, THREE) == 0 and nb(B, 8, 2, 3) == 0
+    # a short workspace: PARROT_E_NOMEM; the fused and flash cores need none but the entry still wants a real one
+    assert nb(B, 33, 2, THREE) >= B * 2 * 33 * 33 * 4 and nb(B, 33, 2, FUSED) > 0 and nb(B, 33, 2, FLASH) > 0
+    assert call(THREE, 16, 33, ws_bytes=B * 2 * 33 * 33 * 4 - 4) == -4
+    # LayerNorm
+    x = torch.zeros((2, 4, 8), device=DEV)
+    g = torch.ones(4, device=DEV)
+    p = ops.dptr
+    assert lib.parrot_debug_layernorm(None, p(g), p(g), p(x), 2, 4, 8, 0, ops.stream_ptr()) == -1
+    assert lib.parrot_debug_layernorm(p(x), p(g), p(g), None, 2, 4, 8, 0, ops.stream_ptr()) == -1
+    assert lib.parrot_debug_layernorm(p(x), p(g), p(g), p(x), 2, 0, 8, 0, ops.stream_ptr()) == -1
+    assert lib.parrot_debug_layernorm(p(x), p(g), p(g), p(x), 0, 4, 8, 0, ops.stream_ptr()) == -1
+    # and the library is fine afterwards
+    qkv, valid, ref, scale, _ = _reference(16, 2, 33, 1.0, MASK_GROUPS[0])
+    assert float((_run(FLASH, qkv, valid, 2).double() - ref).abs().max()) / scale <= 2e-5
+
+
+# ---- LayerNorm ---------------------------------------------------------------------------------------------------------------------
+LN_C = [1, 15, 16, 17, 255, 256, 257, 384, 1000]  # the kernel keeps C <= 256 in registers and re-reads wider layers from memory
+LN_T = [1, 63, 64, 65, 130]
+
+
+@functools.lru_cache(maxsize=None)
+def _ln_case(C, T, relu_in):
+    gen = torch.Generator().manual_seed(31 * C + T)
+    x = torch.randn((2, C, T), generator=gen)
+    x[1] += 10.0  # (per-row offset in {0, 10}: beyond that the fp32 mean itself is the dominant error)
+    g, b = torch.randn(C, generator=gen), torch.randn(C, generator=gen)
+    x64 = x.double().relu() if relu_in else x.double()
+    ref = F.layer_norm(x64.transpose(1, 2), (C,), g.double(), b.double(), 1e-5).transpose(1, 2).contiguous()
+    return x, g, b, ref
+
+
+@pytest.mark.parametrize("C", LN_C)
+def test_layernorm_vs_fp64(C):
+    worst = 0.0
+    try:
+        for T in LN_T:
+            for relu_in in (0, 1):
+                x, g, b, ref = _ln_case(C, T, relu_in)
+                buf, y = _guarded((2, C, T))
+                got = ops.debug_layernorm(x.to(DEV), g.to(DEV), b.to(DEV), bool(relu_in), out=y).cpu()
+                assert _guards_intact(buf), (C, T, relu_in)
+                scale = max(1.0, float(ref.abs().max()))
+                err = float((got.double() - ref).abs().max()) / scale
+                worst = max(worst, err)
+                print(json.dumps(dict(C=C, T=T, relu_in=relu_in, err=err)))
+                assert err <= 2e-5, (C, T, relu_in, err)
+                if C == 1:  # x - mean = 0 exactly: y is beta
+                    assert torch.equal(got, b.view(1, 1, 1).expand(2, 1, T))
+                assert torch.equal(ops.debug_layernorm(x.to(DEV), g.to(DEV), b.to(DEV), bool(relu_in)).cpu(), got)
+    finally:
+        _report(test="layernorm_vs_fp64", C=C, max_err_over_scale=worst)
+
+
+def test_whole_file_under_poison():
+    """This file once more in a child process under PARROT_POISON_WS=nan: a kernel reading a byte of the score workspace or of
+    ctx / y that nobody wrote, or leaving an element of them unwritten, turns a result into NaN there (the NaN rows the tests above
+    expect are compared by position, so poison cannot hide in them)."""
+    if os.environ.get("PARROT_POISON_WS"):
+        return  # (already a poisoned run: the tests above were it)
+    env = dict(os.environ, PARROT_POISON_WS="nan")
+    r = subprocess.run([sys.executable, "-m", "pytest", "-q", "-m", "gpu", "-x", os.path.abspath(__file__), "-k", "not whole_file"], cwd=ROOT,
+                       capture_output=True, text=True, env=env, timeout=600)
+    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]

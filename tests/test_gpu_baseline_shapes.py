@@ -220,6 +220,8 @@ NON_DEFAULT_TTE = [
     dict(enc_heads=4, dec_heads=1, kernels=[3, 3], d_model=64),      # head dims 16 and 64
     dict(enc_heads=1, dec_heads=2, kernels=[5, 1], d_model=128),     # head dims 128 (fused core) and 64
     dict(enc_heads=2, dec_heads=2, kernels=[9, 1], d_model=256),     # the shipped head dim, reduced depth / FFN width
+    dict(enc_heads=2, dec_heads=4, kernels=[3, 1], d_model=96),      # head dims 48 and 24: the three-kernel core under every precision
+    dict(enc_heads=2, dec_heads=2, kernels=[3, 1], d_model=64),      # head dim 32: attn_flash_kernel<32> under f16x3
 ]
 
 
