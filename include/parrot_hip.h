@@ -286,6 +286,24 @@ size_t parrot_tte_loss_workspace_bytes(int32_t N);
 int parrot_tte_loss(const float* logits, const int64_t* targets, int32_t N, int32_t V, int64_t ignore_index, const float* log_dur,
                     const int64_t* dur, const uint8_t* src_mask, int32_t n_src, double* out, float* losses /* nullable */, void* ws,
                     size_t ws_bytes, void* stream);
+/* ModelLoss with its gradient (modules/loss.py:5-21; train.py:72-85: the loss training_step returns and Lightning's
+ * loss.backward()), in one stateless call that runs the forward itself.  out and losses are parrot_tte_loss's for the same inputs,
+ * bit for bit.  weights: DEVICE pointer to {w_code, w_dur} doubles, the gradients arriving at code_loss and dur_loss (a backward
+ * needs no host synchronisation); NULL = {1, 1}, the gradient of losses[0].
+ *   grad_logits (N,V) f32   <- (w_code / n_valid) (softmax(logits[n]) - onehot(targets[n])); a row with targets[n] == ignore_index is
+ *                              exactly 0; a row whose target is outside [0, V) otherwise is NaN (it counts in n_bad; nothing is
+ *                              indexed through the value)
+ *   grad_log_dur (n_src) f32 <- src_mask[i] ? (2 w_dur / n_src valid) (log_dur[i] - log(dur[i] + 1)) : 0
+ * The two quotients are formed in fp64 and rounded to fp32 once.  An all-ignored batch / an empty src_mask: NaN losses (as
+ * parrot_tte_loss) and all-zero gradients, as torch's autograd gives.  Either gradient may be NULL, not both; grad_logits must not
+ * alias logits nor grad_log_dur log_dur (PARROT_E_INVALID).  Every output element is written exactly once; no floating-point
+ * atomics: two calls agree bit for bit, and a row's gradient depends on that row, n_valid and w_code only.  For V % 4 == 0,
+ * V <= 1024 and 16-byte aligned logits the logits are read from memory once.  ws: parrot_tte_loss_grad_workspace_bytes(N). */
+size_t parrot_tte_loss_grad_workspace_bytes(int32_t N);
+int parrot_tte_loss_grad(const float* logits, const int64_t* targets, int32_t N, int32_t V, int64_t ignore_index, const float* log_dur,
+                         const int64_t* dur, const uint8_t* src_mask, int32_t n_src, const double* weights /* device, nullable */,
+                         double* out, float* losses /* nullable */, float* grad_logits /* nullable */,
+                         float* grad_log_dur /* nullable */, void* ws, size_t ws_bytes, void* stream);
 /* Device-side flags.  Synchronises `stream`, clears the flag; returns 0, PARROT_E_RANGE (a bad phone / speaker id <-> the
  * reference's Embedding IndexError) or PARROT_E_NONFINITE (NaN / inf logits at some position of the last decode: an
  * activation beyond the fp16 split scheme's range -- the ids of that call are not to be trusted). */

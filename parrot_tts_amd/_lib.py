@@ -124,6 +124,8 @@ SIGNATURES = {
     "parrot_tte_decode_masked": (C.c_int, [vp, i32, i32, i32, i32, vp, vp, vp, vp, sz, vp, sz, vp]),
     "parrot_tte_loss_workspace_bytes": (sz, [i32]),
     "parrot_tte_loss": (C.c_int, [vp, vp, i32, i32, C.c_int64, vp, vp, vp, i32, vp, vp, vp, sz, vp]),
+    "parrot_tte_loss_grad_workspace_bytes": (sz, [i32]),
+    "parrot_tte_loss_grad": (C.c_int, [vp, vp, i32, i32, C.c_int64, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, sz, vp]),
     "parrot_tte_check": (C.c_int, [vp, vp]),
     "parrot_tte_status_async": (C.c_int, [vp, vp, vp]),
     "parrot_tte_status_peek_async": (C.c_int, [vp, vp, vp]),

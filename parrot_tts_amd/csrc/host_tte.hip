@@ -511,7 +511,7 @@ extern "C" int parrot_tte_decode_masked(parrot_tte_t* t, int32_t B, int32_t S, i
                            key_mask);
 }
 
-// ModelLoss (modules/loss.py:5-21): loss_rows_kernel + loss_reduce_kernel (kernels_misc.h)
+// ModelLoss (modules/loss.py:5-21): loss_rows_kernel + loss_reduce_kernel (kernels_misc.h); with the gradient, loss_count_kernel first
 static size_t loss_ws(Arena& a, int32_t N, double** nll, LossCounts** cnt, int64_t** bad) {
     const size_t nblk = (size_t)std::max((N + LOSS_WAVES - 1) / LOSS_WAVES, 1);
     *nll = a.take<double>(nblk);
@@ -545,7 +545,60 @@ extern "C" int parrot_tte_loss(const float* logits, const int64_t* targets, int3
         TRY(poison(losses, 3 * sizeof(float), s));
     }
     const int nblk = (N + LOSS_WAVES - 1) / LOSS_WAVES;
-    hipLaunchKernelGGL(loss_rows_kernel, dim3(nblk), dim3(64 * LOSS_WAVES), 0, s, logits, targets, N, V, ignore_index, nll, cnt, bad);
+    hipLaunchKernelGGL(loss_rows_kernel<false>, dim3(nblk), dim3(64 * LOSS_WAVES), 0, s, logits, targets, N, V, ignore_index, nll, cnt, bad, nullptr, nullptr);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(loss_reduce_kernel, dim3(1), dim3(LOSS_REDUCE), 0, s, nll, cnt, bad, nblk, log_dur, dur, src_mask, n_src, out, losses);
+    HIP_TRY(hipGetLastError());
+    return PARROT_OK;
+}
+
+// The same with the gradient (train.py:72-85): count + duration gradient, rows + logit gradient, the forward's reduction
+static size_t loss_grad_ws(Arena& a, int32_t N, double** nll, LossCounts** cnt, int64_t** bad, LossScale** scale) {
+    (void)loss_ws(a, N, nll, cnt, bad);
+    *scale = a.take<LossScale>(1);
+    return align_up(a.off, 256);
+}
+extern "C" size_t parrot_tte_loss_grad_workspace_bytes(int32_t N) {
+    if (N < 0) return 0;
+    Arena a(nullptr, 0);
+    double* nll;
+    LossCounts* cnt;
+    int64_t* bad;
+    LossScale* scale;
+    return loss_grad_ws(a, N, &nll, &cnt, &bad, &scale);
+}
+extern "C" int parrot_tte_loss_grad(const float* logits, const int64_t* targets, int32_t N, int32_t V, int64_t ignore_index, const float* log_dur,
+                                    const int64_t* dur, const uint8_t* src_mask, int32_t n_src, const double* weights, double* out, float* losses,
+                                    float* grad_logits, float* grad_log_dur, void* ws, size_t ws_bytes, void* stream) {
+    if (!logits || !targets || !log_dur || !dur || !src_mask || !out || !ws) return fail(PARROT_E_INVALID, "tte_loss_grad: null argument");
+    if (N <= 0 || V <= 0 || n_src < 0) return fail(PARROT_E_INVALID, "tte_loss_grad: empty logits or negative size");
+    if (!grad_logits && !grad_log_dur) return fail(PARROT_E_INVALID, "tte_loss_grad: both gradients null (parrot_tte_loss is the forward alone)");
+    if (grad_logits == logits || grad_log_dur == log_dur) return fail(PARROT_E_INVALID, "tte_loss_grad: a gradient must not alias its input");
+    hipStream_t s = (hipStream_t)stream;
+    Arena a(ws, ws_bytes);
+    double* nll;
+    LossCounts* cnt;
+    int64_t* bad;
+    LossScale* scale;
+    (void)loss_grad_ws(a, N, &nll, &cnt, &bad, &scale);
+    if (!a.ok) return fail(PARROT_E_NOMEM, "tte_loss_grad: workspace too small");
+    if (poison_word()) {
+        TRY(poison(ws, ws_bytes, s));
+        TRY(poison(out, 8 * sizeof(double), s));
+        TRY(poison(losses, 3 * sizeof(float), s));
+        TRY(poison(grad_logits, (size_t)N * V * sizeof(float), s));
+        TRY(poison(grad_log_dur, (size_t)n_src * sizeof(float), s));
+    }
+    const int nblk = (N + LOSS_WAVES - 1) / LOSS_WAVES;
+    hipLaunchKernelGGL(loss_count_kernel, dim3(1), dim3(LOSS_REDUCE), 0, s, targets, N, V, ignore_index, log_dur, dur, src_mask, n_src, weights, scale,
+                       grad_log_dur);
+    HIP_TRY(hipGetLastError());
+    if (grad_logits)
+        hipLaunchKernelGGL(loss_rows_kernel<true>, dim3(nblk), dim3(64 * LOSS_WAVES), 0, s, logits, targets, N, V, ignore_index, nll, cnt, bad, scale,
+                           grad_logits);
+    else
+        hipLaunchKernelGGL(loss_rows_kernel<false>, dim3(nblk), dim3(64 * LOSS_WAVES), 0, s, logits, targets, N, V, ignore_index, nll, cnt, bad, nullptr,
+                           nullptr);
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(loss_reduce_kernel, dim3(1), dim3(LOSS_REDUCE), 0, s, nll, cnt, bad, nblk, log_dur, dur, src_mask, n_src, out, losses);
     HIP_TRY(hipGetLastError());

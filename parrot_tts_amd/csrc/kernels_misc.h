@@ -262,15 +262,56 @@ static __global__ __launch_bounds__(256) void dur_prefix_kernel(const int64_t* _
 // (log_softmax's order), and whether the first-max argmax is the target; each block's 16 positions are added in fp64 in row
 // order.  Stage 2 (one block): the block partials and the duration term, each thread a fixed strided slice, then a fixed LDS
 // tree.  No atomics on values: two calls agree bit for bit.  Reads the logits once (V <= 1024 and 16-byte rows: from registers).
+// The gradient (train.py:72-85, loss.backward()): loss_count_kernel counts the valid targets and the set mask bytes first (the
+// scales w_code / n_valid and 2 w_dur / n_src must be known before a scaled element can be written) and writes the duration
+// gradient; loss_rows_kernel<true> is stage 1 with one more step per row, g_code (softmax - onehot) from the registers that hold
+// the row (an ignored row: zeros, a bad target: NaN); stage 2 is unchanged.  Every output element is written exactly once.
 // ---------------------------------------------------------------------------------------------
 constexpr int LOSS_WAVES = 16;      // positions per stage-1 block
 constexpr int LOSS_CHUNKS = 4;      // float4 per lane held in registers: V <= 1024 on the vector path
-constexpr int LOSS_REDUCE = 1024;   // stage-2 threads
+constexpr int LOSS_REDUCE = 1024;   // stage-2 threads (and loss_count_kernel's)
 struct LossCounts { int32_t n_valid, n_correct, n_bad, first_bad_row; };
+struct LossScale { float g_code, g_dur; int32_t n_valid, n_src; };  // g_code = w_code / n_valid, g_dur = 2 w_dur / n_src: fp64, rounded once
 
+// weights (nullable: {1, 1}) = {w_code, w_dur} fp64; grad_log_dur (nullable) (n_src) <- g_dur (log_dur - log(dur + 1)) under the mask, 0 elsewhere
+static __global__ __launch_bounds__(LOSS_REDUCE) void loss_count_kernel(const int64_t* __restrict__ tgt, int N, int V, int64_t ignore,
+                                                                        const float* __restrict__ log_dur, const int64_t* __restrict__ dur,
+                                                                        const uint8_t* __restrict__ src_mask, int n_src,
+                                                                        const double* __restrict__ weights, LossScale* __restrict__ scale,
+                                                                        float* __restrict__ grad_log_dur) {
+    __shared__ int s_valid[LOSS_REDUCE], s_src[LOSS_REDUCE];
+    const int tid = threadIdx.x;
+    int nv = 0, ns = 0;
+    for (int i = tid; i < N; i += LOSS_REDUCE) {
+        const int64_t t = tgt[i];
+        nv += t != ignore && t >= 0 && t < V;  // loss_rows_kernel's states 1 and 2
+    }
+    for (int i = tid; i < n_src; i += LOSS_REDUCE) ns += src_mask[i] != 0;
+    s_valid[tid] = nv; s_src[tid] = ns;
+    __syncthreads();
+    for (int h = LOSS_REDUCE / 2; h > 0; h >>= 1) {
+        if (tid < h) {
+            s_valid[tid] += s_valid[tid + h];
+            s_src[tid] += s_src[tid + h];
+        }
+        __syncthreads();
+    }
+    nv = s_valid[0]; ns = s_src[0];
+    const double w_code = weights ? weights[0] : 1.0, w_dur = weights ? weights[1] : 1.0;
+    // (nothing valid: the quotient is inf or NaN and multiplies nothing -- every row is ignored, every mask byte clear)
+    const float g_code = (float)(w_code / (double)nv), g_dur = (float)(2.0 * w_dur / (double)ns);
+    if (tid == 0) *scale = LossScale{g_code, g_dur, nv, ns};
+    if (grad_log_dur)
+        for (int i = tid; i < n_src; i += LOSS_REDUCE)
+            grad_log_dur[i] = src_mask[i] ? g_dur * (log_dur[i] - logf((float)dur[i] + 1.0f)) : 0.f;  // the forward's difference
+}
+
+// GRAD: also grad (N, V) <- scale->g_code (softmax(x) - onehot(target)) per valid row, 0 for an ignored one, NaN for a bad target
+template <bool GRAD>
 static __global__ __launch_bounds__(64 * LOSS_WAVES) void loss_rows_kernel(const float* __restrict__ logits, const int64_t* __restrict__ tgt,
                                                                          int N, int V, int64_t ignore, double* __restrict__ part_nll,
-                                                                         LossCounts* __restrict__ part_cnt, int64_t* __restrict__ part_bad) {
+                                                                         LossCounts* __restrict__ part_cnt, int64_t* __restrict__ part_bad,
+                                                                         const LossScale* __restrict__ scale, float* __restrict__ grad) {
     __shared__ double s_nll[LOSS_WAVES];
     __shared__ int s_st[LOSS_WAVES];  // 0 skipped, 1 valid, 2 valid and argmax == target, 3 target out of range
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -290,10 +331,29 @@ static __global__ __launch_bounds__(64 * LOSS_WAVES) void loss_rows_kernel(const
             }
         }
         const int64_t tg = tgt[row];
-        if (tg == ignore) {
-            st = 0;
-        } else if (tg < 0 || tg >= V) {
-            st = 3;
+        float* __restrict__ g = GRAD ? grad + (size_t)row * V : nullptr;
+        const bool gvec = ((uintptr_t)grad & 15) == 0;  // (V % 4 == 0 on the vector path: every row of an aligned base is aligned)
+        auto put4 = [&](int i, float a, float b, float c, float d) {
+            if (gvec) {
+                *reinterpret_cast<float4*>(g + i) = make_float4(a, b, c, d);
+            } else {
+                g[i] = a; g[i + 1] = b; g[i + 2] = c; g[i + 3] = d;
+            }
+        };
+        if (tg == ignore || tg < 0 || tg >= V) {
+            st = tg == ignore ? 0 : 3;
+            if constexpr (GRAD) {  // an ignored row is 0 throughout; nothing is indexed through a bad target: its row is NaN
+                const float fill = st == 0 ? 0.f : NAN;
+                if (vec) {
+#pragma unroll
+                    for (int k = 0; k < LOSS_CHUNKS; ++k) {
+                        const int i = (k * 64 + lane) * 4;
+                        if (i < V) put4(i, fill, fill, fill, fill);
+                    }
+                } else {
+                    for (int i = lane; i < V; i += 64) g[i] = fill;
+                }
+            }
         } else {
             const float xt = x[tg];
             float m = -INFINITY, s = 0.f;
@@ -333,6 +393,21 @@ static __global__ __launch_bounds__(64 * LOSS_WAVES) void loss_rows_kernel(const
             s = wave_sum(s);
             nll = (double)(logf(s) - (xt - m));
             st = mi == (int)tg ? 2 : 1;
+            if constexpr (GRAD) {
+                const float gc = scale->g_code, inv = 1.0f / s;
+                const int t = (int)tg;
+                if (vec) {  // from the registers that hold the row
+#pragma unroll
+                    for (int k = 0; k < LOSS_CHUNKS; ++k) {
+                        const int i = (k * 64 + lane) * 4;
+                        if (i < V)
+                            put4(i, gc * (expf(r[k].x - m) * inv - (i == t ? 1.f : 0.f)), gc * (expf(r[k].y - m) * inv - (i + 1 == t ? 1.f : 0.f)),
+                                 gc * (expf(r[k].z - m) * inv - (i + 2 == t ? 1.f : 0.f)), gc * (expf(r[k].w - m) * inv - (i + 3 == t ? 1.f : 0.f)));
+                    }
+                } else {  // a third pass, from cache
+                    for (int i = lane; i < V; i += 64) g[i] = gc * (expf(x[i] - m) * inv - (i == t ? 1.f : 0.f));
+                }
+            }
         }
     }
     if (lane == 0) {
