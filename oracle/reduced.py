@@ -120,7 +120,7 @@ def reduced_layer(kind: str, c_in: int, c_out: int, k: int, stride: int = 1, *, 
     if kind not in ("conv", "convt", "rb"):
         raise ValueError(f"unknown layer kind {kind!r}")
     transposed = kind == "convt"
-    # parrot_hip.hip voc_create: a ResBlock1 whose (channels, k) the pair kernels take gets a concatenated weight stream
+    # host_voc_mrf.hip mrf_create: a ResBlock1 whose (channels, k) the pair kernels take gets a concatenated weight stream
     # (`rb_stream`, needs a split scheme), and voc_forward runs it on resblock_split_launch whenever `v->fused != 0` -- also
     # at 16 channels, where the layer plans themselves are exact (rows < 32, below)
     if kind == "rb" and fused != 0 and resblock_type == 1 and resblock_split_has(c_out, k) and 2 * n_dil <= RBS_MAX_CONVS:

@@ -1,6 +1,6 @@
 """Build libparrot_hip.so in-tree with hipcc for gfx950 (cross-compiles without a GPU).  Every csrc/*.hip is one translation unit,
-compiled in parallel, then linked: host_*.hip and parrot_hip.hip (the vocoder) hold the C ABI, one unit per subsystem (shared
-declarations in host_common.h), tu_*.hip instantiate the kernel templates."""
+compiled in parallel, then linked: host_*.hip hold the C ABI, one unit per subsystem (three for the vocoder, host_voc*.hip, around voc.h;
+shared declarations in host_common.h), tu_*.hip instantiate the kernel templates."""
 from __future__ import annotations
 
 import os

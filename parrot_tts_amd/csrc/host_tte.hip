@@ -659,14 +659,23 @@ extern "C" int parrot_tte_debug_stages(parrot_tte_t* t, float* const* enc_ptrs, 
 }
 
 // length_regulator on its own (duration.py:6-24): channel-last in / out around the decoder's kernel
+struct LrScratch {
+    float *seq_cf, *out_cf, *zero;  // channel-first input (B, D, S) and output (B, D, L), a zero vector (D)
+    int32_t *cum, *lens;
+};
+static LrScratch lr_scratch(Arena& a, int B, int S, int D, int L) {
+    LrScratch w{};
+    w.seq_cf = a.take<float>((size_t)B * D * S);
+    w.out_cf = a.take<float>((size_t)B * D * L);
+    w.zero = a.take<float>((size_t)D);
+    w.cum = a.take<int32_t>((size_t)B * S);
+    w.lens = a.take<int32_t>((size_t)B);
+    return w;
+}
 extern "C" size_t parrot_length_regulator_workspace_bytes(int32_t B, int32_t S, int32_t D, int32_t L) {
     if (B <= 0 || S <= 0 || D <= 0 || L < 0) return 0;
     Arena a(nullptr, 0);
-    a.take<float>((size_t)B * D * S);
-    a.take<float>((size_t)B * D * std::max(L, 1));
-    a.take<float>((size_t)D);
-    a.take<int32_t>((size_t)B * S);
-    a.take<int32_t>((size_t)B);
+    (void)lr_scratch(a, B, S, D, std::max(L, 1));
     return align_up(a.off, 256);
 }
 extern "C" int parrot_length_regulator(const float* seq, const int64_t* dur, int32_t B, int32_t S, int32_t D, int32_t L, float* out,
@@ -675,11 +684,7 @@ extern "C" int parrot_length_regulator(const float* seq, const int64_t* dur, int
     if (B <= 0 || S <= 0 || D <= 0 || L <= 0) return fail(PARROT_E_INVALID, "length_regulator: empty batch or L = 0");
     hipStream_t s = (hipStream_t)stream;
     Arena a(ws, ws_bytes);
-    float* seq_cf = a.take<float>((size_t)B * D * S);
-    float* out_cf = a.take<float>((size_t)B * D * L);
-    float* zero = a.take<float>((size_t)D);
-    int32_t* cum = a.take<int32_t>((size_t)B * S);
-    int32_t* lens = a.take<int32_t>((size_t)B);
+    const LrScratch w = lr_scratch(a, B, S, D, L);
     if (!a.ok) return fail(PARROT_E_NOMEM, "length_regulator: workspace too small");
     if (poison_word()) {
         TRY(poison(ws, ws_bytes, s));
@@ -687,14 +692,14 @@ extern "C" int parrot_length_regulator(const float* seq, const int64_t* dur, int
         TRY(poison(mask, (size_t)B * L, s));
         TRY(poison(out_lens, (size_t)B * sizeof(int32_t), s));
     }
-    HIP_TRY(hipMemsetAsync(zero, 0, (size_t)D * sizeof(float), s));
+    HIP_TRY(hipMemsetAsync(w.zero, 0, (size_t)D * sizeof(float), s));
     // (B,S,D) -> (B,D,S): the transpose kernel with the roles of C and T swapped
-    hipLaunchKernelGGL(transpose_cf_to_cl_kernel, dim3((D + 63) / 64, (S + 63) / 64, B), dim3(256), 0, s, seq, seq_cf, S, D);
-    hipLaunchKernelGGL(dur_prefix_kernel, dim3(B), dim3(256), 0, s, dur, cum, lens, S);
-    hipLaunchKernelGGL(length_regulate_kernel, dim3((L + 63) / 64, B), dim3(256), 0, s, seq_cf, cum, lens, zero, out_cf, mask, S, L, D, nullptr, 1, 0, 0);
-    hipLaunchKernelGGL(transpose_cf_to_cl_kernel, dim3((L + 63) / 64, (D + 63) / 64, B), dim3(256), 0, s, out_cf, out, D, L);
+    hipLaunchKernelGGL(transpose_cf_to_cl_kernel, dim3((D + 63) / 64, (S + 63) / 64, B), dim3(256), 0, s, seq, w.seq_cf, S, D);
+    hipLaunchKernelGGL(dur_prefix_kernel, dim3(B), dim3(256), 0, s, dur, w.cum, w.lens, S);
+    hipLaunchKernelGGL(length_regulate_kernel, dim3((L + 63) / 64, B), dim3(256), 0, s, w.seq_cf, w.cum, w.lens, w.zero, w.out_cf, mask, S, L, D, nullptr, 1, 0, 0);
+    hipLaunchKernelGGL(transpose_cf_to_cl_kernel, dim3((L + 63) / 64, (D + 63) / 64, B), dim3(256), 0, s, w.out_cf, out, D, L);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(out_lens, lens, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+    HIP_TRY(hipMemcpyAsync(out_lens, w.lens, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
     return PARROT_OK;
 }
 

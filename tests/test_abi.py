@@ -68,6 +68,19 @@ def test_abi_basics(lib):
     assert b"null" in lib.parrot_last_error()
 
 
+def test_length_regulator_workspace_bytes_are_the_recorded_ones(lib):
+    """The query sizes with the layout function that parrot_length_regulator carves with (lr_scratch, host_tte.hip), reserving
+    max(L, 1) output columns: same bytes as before the two were unified (tests/golden/workspace_bytes.json, recorded by
+    tools/make_workspace_goldens.py).  Needs no device."""
+    import json
+    with open(os.path.join(ROOT, "tests", "golden", "workspace_bytes.json")) as f:
+        golden = json.load(f)["length_regulator"]
+    for B, S, D, L in [(1, 1, 1, 0), (2, 7, 256, 0), (2, 7, 256, 33), (64, 64, 256, 2048)]:
+        assert lib.parrot_length_regulator_workspace_bytes(B, S, D, L) == golden[f"{B},{S},{D},{L}"], (B, S, D, L)
+    for B, S, D in [(0, 7, 256), (-1, 7, 256), (2, 0, 256), (2, -3, 256), (2, 7, 0), (2, 7, -1)]:
+        assert lib.parrot_length_regulator_workspace_bytes(B, S, D, 33) == 0, (B, S, D)
+
+
 def test_struct_sizes_match_header():
     from parrot_tts_amd import _lib
     assert ctypes.sizeof(_lib.ConvDesc) == 12 * 4

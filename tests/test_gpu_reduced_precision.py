@@ -481,7 +481,7 @@ def _mrf_single_pair(w, h, i, x, mode, fused, variant="rne"):
 
 # (case, B, U, stages checked): full_u40 reaches every channel count's pair kernels (per-branch launches) and, at 256 / 128 /
 # 64 channels, the layer plans with operand planes; full_b8_u256's 32-channel stage fills the chip twice over
-# (B ceil(T / 648) >= 512 workgroups), which voc_forward runs as ONE whole-MRF launch (parrot_hip.hip, mrf_split_launch)
+# (B ceil(T / 648) >= 512 workgroups), which voc_forward runs as ONE whole-MRF launch (host_voc_mrf.hip, mrf_split_launch)
 # Teeth: bf16 -- 20 x the bound against no rounding, and both truncation and leaky ReLU after the intermediate rounding fail.
 # fp16's grid is 8 x finer: far more intermediate operands lie within accumulation noise of a rounding midpoint, and the flip
 # allowance for them (one grid step through |w2| each) grows to a few times the rounding effect itself at 256 channels (emulated:

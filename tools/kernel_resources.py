@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Summarise hipcc's -Rpass-analysis=kernel-resource-usage remarks: registers, scratch (spills), occupancy per kernel.
-    hipcc --offload-arch=gfx950 -O3 -std=c++17 -c --cuda-device-only -Rpass-analysis=kernel-resource-usage parrot_hip.hip -o /dev/null 2> res.txt
+    hipcc --offload-arch=gfx950 -O3 -std=c++17 -c --cuda-device-only -Rpass-analysis=kernel-resource-usage host_voc_mrf.hip -o /dev/null 2> res.txt
     python tools/kernel_resources.py res.txt [substring]"""
 import re
 import subprocess
