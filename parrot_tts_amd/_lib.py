@@ -196,6 +196,32 @@ def check(code: int) -> None:
         raise ParrotHipError(code, lib().parrot_last_error().decode())
 
 
+E_RANGE, E_NONFINITE = -2, -6  # PARROT_E_RANGE, PARROT_E_NONFINITE of include/parrot_hip.h
+ST_NONFINITE = 5  # device status word of every handle kind: a non-finite output (csrc/kernels_misc.h, aligner.h, mel.h)
+
+
+def reraise(e: ParrotHipError, on_nonfinite=None):
+    """Inside ``except ParrotHipError as e``: PARROT_E_RANGE <-> the reference's IndexError (pe[T], Embedding), PARROT_E_NONFINITE
+    (a flag raised by an earlier run) -> FloatingPointError, same message, chain suppressed; anything else is raised as it is.
+    ``on_nonfinite``: called before the FloatingPointError is raised."""
+    if e.code == E_RANGE:
+        raise IndexError(str(e)) from None
+    if e.code == E_NONFINITE:
+        if on_nonfinite is not None:
+            on_nonfinite()
+        raise FloatingPointError(str(e)) from None
+    raise e
+
+
+def destroy(fn_name: str, handle) -> None:
+    """The one guarded destroy (invalidation and every ``__del__``): nothing for a null handle, and nothing once module globals
+    are gone -- `_lib` is None again while the interpreter tears down (and a live handle means the library was loaded).
+    At that time the CALLER's globals are going too, this function among them: a ``__del__`` reaches it through a default
+    argument bound at definition time (``_destroy=_lib.destroy``), never through its module's global ``_lib``."""
+    if handle and _lib is not None:
+        getattr(_lib, fn_name)(handle)
+
+
 def fptr(t):
     """Host fp32 pointer of a contiguous CPU float tensor (caller keeps `t` alive)."""
     assert t.device.type == "cpu" and t.dtype.is_floating_point and t.is_contiguous()

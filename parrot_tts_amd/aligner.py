@@ -22,17 +22,19 @@ own choice there follows no fixed rule.  There is no CPU path: a CPU
 from __future__ import annotations
 
 import ctypes as C
-from typing import Dict, Optional, Tuple
+from typing import Dict, Tuple
 
 import numpy as np
 import torch
 from torch import nn
 
 from . import _lib
-from .ops import PREC_NAMES, PREC_STR, dptr, param_fingerprint, require_cuda, stream_ptr
+from ._handle import PackedHandleModule, _attach
+from ._lib import ST_NONFINITE
+from .ops import _prec_arg, _workspace, dptr, param_fingerprint, require_cuda, stream_ptr
 
 MAX_FRAMES, MAX_TOKENS = 32768, 2048  # csrc/aligner.h: ALIGN_MAX_T, ALIGN_MAX_N
-ST_NONFINITE, ST_BAD_INPUT = 5, 9
+ST_BAD_INPUT = 9
 BN_EPS = 1e-5
 
 
@@ -54,29 +56,18 @@ def aligner_param_shapes(n_mels: int, num_symbols: int, lstm_dim: int, conv_dim:
     return sh
 
 
-def _attach(root: nn.Module, dotted: str, tensor: torch.Tensor, buffer: bool) -> None:
-    parts = dotted.split(".")
-    m = root
-    for p in parts[:-1]:
-        if p not in m._modules:
-            m.add_module(p, nn.Module())
-        m = m._modules[p]
-    if buffer:
-        m.register_buffer(parts[-1], tensor)
-    else:
-        m.register_parameter(parts[-1], nn.Parameter(tensor))
-
-
-class Aligner(nn.Module):
+class Aligner(PackedHandleModule):
     """Inference-only counterpart of the reference's ``Aligner``: the same constructor, ``state_dict`` keys (``step`` and the
     BatchNorm buffers included), ``from_checkpoint`` and ``get_step``; ``forward`` runs on the HIP kernels.  BatchNorm uses its
     running statistics (the reference's ``.eval()``); ``step`` increments on every forward, as the reference's does in eval too
     (``if self.train:`` tests a bound method)."""
 
+    _destroy_fn, _precision_fn = "parrot_aligner_destroy", "parrot_aligner_precision"
+
     def __init__(self, n_mels: int, num_symbols: int, lstm_dim: int, conv_dim: int, precision=None) -> None:
         super().__init__()
         self.n_mels, self.num_symbols, self.lstm_dim, self.conv_dim = int(n_mels), int(num_symbols), int(lstm_dim), int(conv_dim)
-        self.precision = -1 if precision is None else (PREC_NAMES[precision] if isinstance(precision, str) else int(precision))
+        self.precision = _prec_arg(precision)
         self.register_buffer("step", torch.tensor(1, dtype=torch.int))
         gen = torch.Generator().manual_seed(0)
         for key, shape in aligner_param_shapes(self.n_mels, self.num_symbols, self.lstm_dim, self.conv_dim).items():
@@ -94,11 +85,7 @@ class Aligner(nn.Module):
             _attach(self, key, t, buffer=False)
         for i in range(3):
             _attach(self, f"convs.{i}.bnorm.num_batches_tracked", torch.tensor(0, dtype=torch.long), buffer=True)
-        self._handle: Optional[C.c_void_p] = None
-        self._handle_device = None
-        self._handle_fp = None
         self._taps = None
-        self.register_load_state_dict_post_hook(lambda module, incompatible: module._invalidate())
 
     # ---- the reference's surface ---------------------------------------------------------------
     def get_step(self):
@@ -112,36 +99,13 @@ class Aligner(nn.Module):
         model.load_state_dict(checkpoint["model"])
         return model
 
-    # ---- HIP handle ----------------------------------------------------------------------------
-    def _invalidate(self):
-        if self._handle is not None:
-            _lib.lib().parrot_aligner_destroy(self._handle)
-        self._handle = None
-
-    def _apply(self, fn, recurse=True):
-        self._invalidate()
-        return super()._apply(fn, recurse)
-
-    def __del__(self):
-        try:
-            self._invalidate()
-        except Exception:
-            pass
-
+    # ---- HIP handle (lifecycle: _handle.py) -----------------------------------------------------
     def _weight_fingerprint(self):
         step, self._buffers["step"] = self._buffers["step"], None  # (step changes on every forward and is no weight)
         try:
             return param_fingerprint(self)
         finally:
             self._buffers["step"] = step
-
-    def _current_handle(self, dev):
-        fp = self._weight_fingerprint()
-        if self._handle is None or self._handle_device != dev or self._handle_fp != fp:
-            self._invalidate()
-            self._build(dev)
-            self._handle_fp = fp
-        return self._handle
 
     def _build(self, device):
         sd = {k: v.detach().to("cpu", torch.float32).contiguous() for k, v in self.state_dict().items() if v.dim() > 0}
@@ -160,11 +124,6 @@ class Aligner(nn.Module):
         with torch.cuda.device(device):
             _lib.check(_lib.lib().parrot_aligner_create_ex(C.byref(hdl), C.byref(cfg), C.byref(w), self.precision))
         self._handle, self._handle_device = hdl, device
-
-    @property
-    def precision_in_use(self) -> Optional[str]:
-        """Precision of the live handle ("f16x3", "bf16x6", "f32"; None before the first forward)."""
-        return None if self._handle is None else PREC_STR[int(_lib.lib().parrot_aligner_precision(self._handle))]
 
     # ---- compute -------------------------------------------------------------------------------
     def _check_mel(self, mel: torch.Tensor) -> torch.Tensor:
@@ -192,7 +151,7 @@ class Aligner(nn.Module):
                 lstm = torch.empty((B, T, 2 * self.lstm_dim), dtype=torch.float32, device=dev)
             _lib.check(lib.parrot_aligner_debug_stages(h, dptr(bn3), dptr(lstm)))
             n_ws = int(lib.parrot_aligner_workspace_bytes(h, B, T))
-            ws = torch.empty(max(n_ws, 1), dtype=torch.uint8, device=dev)
+            ws = _workspace(n_ws, dev)
             try:
                 _lib.check(lib.parrot_aligner_forward(h, dptr(mel), B, T, dptr(logits), dptr(ws), n_ws, stream_ptr(dev)))
             finally:
@@ -274,6 +233,18 @@ def _ragged_args(who: str, x: torch.Tensor, name: str, tokens, mel_len, tokens_l
     return x, tokens, ml, tl
 
 
+def _call_with_status(who: str, ws_bytes_fn, ws_args: tuple, fn, args: tuple, dev, V: int, what: str) -> None:
+    """What the three calls without a handle share: a workspace whose first word is the device status, the call on the current
+    stream, one read-back of that word (the synchronisation of the call) and ``_raise_status``.  ``args``: everything before
+    (ws, ws_bytes, stream)."""
+    with torch.cuda.device(dev):
+        n_ws = int(ws_bytes_fn(*ws_args))
+        ws = _workspace(n_ws, dev, at_least=4)
+        _lib.check(fn(*args, dptr(ws), n_ws, stream_ptr(dev)))
+        status = int(ws[:4].view(torch.int32).item())
+    _raise_status(who, status, V, what)
+
+
 def _raise_status(who: str, status: int, V: int, what: str) -> None:
     if status == ST_BAD_INPUT:
         raise ValueError(f"{who}: a token outside [0, {V}) or a length outside [1, T] / [1, N] (device status {status})")
@@ -295,13 +266,8 @@ def align_durations(pred: torch.Tensor, tokens: torch.Tensor, mel_len, tokens_le
     lib = _lib.lib()
     dur = torch.empty((B, N), dtype=torch.int32, device=dev)
     cost = torch.empty((B,), dtype=torch.float64, device=dev)
-    with torch.cuda.device(dev):
-        n_ws = int(lib.parrot_align_workspace_bytes(B, T, N))
-        ws = torch.empty(max(n_ws, 4), dtype=torch.uint8, device=dev)
-        _lib.check(lib.parrot_align_durations(dptr(pred), dptr(tokens), dptr(ml), dptr(tl), B, T, V, N, dptr(dur), dptr(cost), dptr(ws),
-                                              n_ws, stream_ptr(dev)))
-        status = int(ws[:4].view(torch.int32).item())
-    _raise_status("align_durations", status, V, "probability in pred")
+    _call_with_status("align_durations", lib.parrot_align_workspace_bytes, (B, T, N), lib.parrot_align_durations,
+                      (dptr(pred), dptr(tokens), dptr(ml), dptr(tl), B, T, V, N, dptr(dur), dptr(cost)), dev, V, "probability in pred")
     return dur, cost
 
 
@@ -321,13 +287,8 @@ def ctc_loss(logits: torch.Tensor, tokens: torch.Tensor, mel_len, tokens_len, re
     lib = _lib.lib()
     nll = torch.empty((B,), dtype=torch.float64, device=dev)
     mean = torch.empty((), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        n_ws = int(lib.parrot_ctc_workspace_bytes(B, T, N))
-        ws = torch.empty(max(n_ws, 4), dtype=torch.uint8, device=dev)
-        _lib.check(lib.parrot_ctc_loss(dptr(logits), dptr(tokens), dptr(ml), dptr(tl), B, T, V, N, dptr(nll), dptr(mean), dptr(ws), n_ws,
-                                       stream_ptr(dev)))
-        status = int(ws[:4].view(torch.int32).item())
-    _raise_status("ctc_loss", status, V, "logit in a real frame")
+    _call_with_status("ctc_loss", lib.parrot_ctc_workspace_bytes, (B, T, N), lib.parrot_ctc_loss,
+                      (dptr(logits), dptr(tokens), dptr(ml), dptr(tl), B, T, V, N, dptr(nll), dptr(mean)), dev, V, "logit in a real frame")
     if reduction == "mean":
         return mean
     return nll if reduction == "none" else nll.sum()
@@ -369,13 +330,9 @@ def _ctc_grad_call(logits, tokens, ml, tl, row_weight, zero_infinity: bool) -> T
     nll = torch.empty((B,), dtype=torch.float64, device=dev)
     grad = torch.empty((B, T, V), dtype=torch.float32, device=dev)
     row_weight = row_weight.to(dev, torch.float64).contiguous()
-    with torch.cuda.device(dev):
-        n_ws = int(lib.parrot_ctc_grad_workspace_bytes(B, T, V, N))
-        ws = torch.empty(max(n_ws, 4), dtype=torch.uint8, device=dev)
-        _lib.check(lib.parrot_ctc_loss_grad(dptr(logits), dptr(tokens), dptr(ml), dptr(tl), B, T, V, N, dptr(row_weight), int(bool(zero_infinity)),
-                                            dptr(nll), dptr(grad), dptr(ws), n_ws, stream_ptr(dev)))
-        status = int(ws[:4].view(torch.int32).item())
-    _raise_status("ctc_loss_and_grad", status, V, "logit in a real frame")
+    _call_with_status("ctc_loss_and_grad", lib.parrot_ctc_grad_workspace_bytes, (B, T, V, N), lib.parrot_ctc_loss_grad,
+                      (dptr(logits), dptr(tokens), dptr(ml), dptr(tl), B, T, V, N, dptr(row_weight), int(bool(zero_infinity)), dptr(nll),
+                       dptr(grad)), dev, V, "logit in a real frame")
     return nll, grad
 
 

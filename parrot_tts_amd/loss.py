@@ -16,7 +16,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from .ops import dptr, require_cuda, stream_ptr
+from .ops import _workspace, dptr, require_cuda, stream_ptr
 
 
 def _loss_call(a, weights=None, grad_logits: bool = False, grad_log_dur: bool = False):
@@ -31,13 +31,13 @@ def _loss_call(a, weights=None, grad_logits: bool = False, grad_log_dur: bool = 
     losses = torch.empty(3, dtype=torch.float32, device=dev)
     with torch.cuda.device(dev):
         if not (grad_logits or grad_log_dur):
-            ws = torch.empty(max(int(lib.parrot_tte_loss_workspace_bytes(N)), 1), dtype=torch.uint8, device=dev)
+            ws = _workspace(lib.parrot_tte_loss_workspace_bytes(N), dev)
             _lib.check(lib.parrot_tte_loss(dptr(logits), dptr(codes), N, V, V, dptr(log_dur), dptr(dur), dptr(src), src.numel(),
                                            dptr(sums), dptr(losses), dptr(ws), ws.numel(), stream_ptr(dev)))
             return sums, losses, None, None
         g_logits = torch.empty_like(logits) if grad_logits else None
         g_dur = torch.empty_like(log_dur) if grad_log_dur else None
-        ws = torch.empty(max(int(lib.parrot_tte_loss_grad_workspace_bytes(N)), 1), dtype=torch.uint8, device=dev)
+        ws = _workspace(lib.parrot_tte_loss_grad_workspace_bytes(N), dev)
         _lib.check(lib.parrot_tte_loss_grad(dptr(logits), dptr(codes), N, V, V, dptr(log_dur), dptr(dur), dptr(src), src.numel(),
                                             dptr(weights), dptr(sums), dptr(losses), dptr(g_logits), dptr(g_dur), dptr(ws), ws.numel(),
                                             stream_ptr(dev)))

@@ -22,7 +22,7 @@ import torch
 from torch import nn
 
 from . import _lib
-from .ops import PREC_NAMES, PREC_STR, dptr, require_cuda, stream_ptr
+from .ops import PREC_STR, _prec_arg, _workspace, dptr, require_cuda, stream_ptr
 
 
 # ---------------------------------------------------------------------------------------------
@@ -108,7 +108,7 @@ class MelSpectrogram:
         self.fmax = float(self.sampling_rate) / 2 if fmax is None else fmax
         self.n_freq = self.n_fft // 2 + 1
         self.pad = (self.n_fft - self.hop_size) // 2
-        self.precision = -1 if precision is None else (PREC_NAMES[precision] if isinstance(precision, str) else int(precision))
+        self.precision = _prec_arg(precision)
         basis = slaney_mel_basis(self.sampling_rate, self.n_fft, self.num_mels, self.fmin, self.fmax) if basis is None else basis
         self.basis = torch.from_numpy(np.ascontiguousarray(basis, dtype=np.float32))
         if tuple(self.basis.shape) != (self.num_mels, self.n_freq):
@@ -173,7 +173,7 @@ class MelSpectrogram:
         out = torch.empty((B, self.num_mels, N // self.hop_size), dtype=torch.float32, device=dev)
         with torch.cuda.device(dev):
             h = self._handle(dev)
-            ws = torch.empty(max(int(lib.parrot_mel_workspace_bytes(h, B, N)), 1), dtype=torch.uint8, device=dev)
+            ws = _workspace(lib.parrot_mel_workspace_bytes(h, B, N), dev)
             _lib.check(lib.parrot_mel_forward(h, dptr(wav), wav.stride(0), dptr(ns), B, N, dptr(out), dptr(ws), ws.numel(), stream_ptr(dev)))
             if check:
                 self.check(dev)
@@ -206,7 +206,7 @@ class MelSpectrogram:
         grad = torch.empty((B, N), dtype=torch.float32, device=dev)
         with torch.cuda.device(dev):
             h = self._handle(dev)
-            ws = torch.empty(max(int(lib.parrot_mel_l1_grad_workspace_bytes(h, B, N)), 1), dtype=torch.uint8, device=dev)
+            ws = _workspace(lib.parrot_mel_l1_grad_workspace_bytes(h, B, N), dev)
             _lib.check(lib.parrot_mel_l1_grad(h, dptr(wav), wav.stride(0), dptr(ns), dptr(target), B, N, 0 if mean else 1, 1.0,
                                               dptr(out), dptr(loss), dptr(grad), dptr(ws), ws.numel(), stream_ptr(dev)))
             self.check(dev)
@@ -219,13 +219,9 @@ class MelSpectrogram:
         with torch.cuda.device(dev):
             _lib.check(_lib.lib().parrot_mel_check(self._handle(dev), stream_ptr(dev)))
 
-    def __del__(self):
+    def __del__(self, _destroy=_lib.destroy):  # (bound here: module globals are already torn down at interpreter exit)
         for h in getattr(self, "_handles", {}).values():
-            if h and _lib is not None:  # (module globals are already torn down at interpreter exit)
-                try:
-                    _lib.lib().parrot_mel_destroy(h)
-                except Exception:
-                    pass
+            _destroy("parrot_mel_destroy", h)
 
 
 _cache = {}  # the reference keeps mel_basis / hann_window in module globals keyed by fmax and device (dataset.py:49-53)
@@ -267,7 +263,7 @@ def mel_l1(a: torch.Tensor, b: torch.Tensor, n_frames=None) -> Tuple[torch.Tenso
     out = torch.empty(2 * B, dtype=torch.float64, device=dev)
     mean = torch.empty((), dtype=torch.float32, device=dev)
     with torch.cuda.device(dev):
-        ws = torch.empty(max(int(lib.parrot_mel_l1_workspace_bytes(B, M, T)), 1), dtype=torch.uint8, device=dev)
+        ws = _workspace(lib.parrot_mel_l1_workspace_bytes(B, M, T), dev)
         _lib.check(lib.parrot_mel_l1(dptr(a), dptr(b), dptr(nf), B, M, T, dptr(out), dptr(mean), dptr(ws), ws.numel(), stream_ptr(dev)))
     return mean, out[:B] / out[B:]
 

@@ -21,6 +21,11 @@ PREC_DEFAULT = PREC_F16X3
 PREC_STR = {v: k for k, v in PREC_NAMES.items()}
 
 
+def _prec_arg(precision) -> int:
+    """A precision argument -- None, a name ("f16x3") or a PARROT_PREC_* code -- as the create calls take it (-1: library default)."""
+    return -1 if precision is None else (PREC_NAMES[precision] if isinstance(precision, str) else int(precision))
+
+
 def set_default_precision(prec: int) -> None:
     """Library-wide default for handles created afterwards (include/parrot_hip.h PARROT_PREC_*): PREC_F32 exact fp32
     MFMA, PREC_F16X3 (default) / PREC_BF16X6 split schemes with fp32-class error, PREC_BF16 / PREC_F16 single-MFMA
@@ -53,6 +58,12 @@ def stream_ptr(device=None) -> C.c_void_p:
 
 def dptr(t: Optional[torch.Tensor]) -> C.c_void_p:
     return C.c_void_p(0 if t is None else t.data_ptr())
+
+
+def _workspace(n_bytes, device, at_least: int = 1) -> torch.Tensor:
+    """Scratch of ``n_bytes`` (what a ``*_workspace_bytes`` call returned) on ``device`` for one library call.  Never of size
+    zero: an empty tensor's pointer is null, which the library takes for a missing argument."""
+    return torch.empty(max(int(n_bytes), at_least), dtype=torch.uint8, device=device)
 
 
 def require_cuda(t: torch.Tensor, name: str) -> None:
@@ -123,13 +134,9 @@ class ConvPlan:
         _lib.check(_lib.lib().parrot_conv_run(self._h, dptr(x), dptr(res), dptr(out), B, T, int(epilogue), float(div), stream_ptr(x.device)))
         return out
 
-    def __del__(self):
+    def __del__(self, _destroy=_lib.destroy):  # (bound here: module globals are already torn down at interpreter exit)
         h, self._h = getattr(self, "_h", None), None
-        if h and _lib is not None:  # (module globals are already torn down at interpreter exit)
-            try:
-                _lib.lib().parrot_conv_destroy(h)
-            except Exception:
-                pass
+        _destroy("parrot_conv_destroy", h)
 
 
 def wav_to_int16(wav: torch.Tensor) -> torch.Tensor:
@@ -153,7 +160,7 @@ def length_regulator(seq: torch.Tensor, dur: torch.Tensor):
     if L <= 0:
         raise ValueError("length_regulator: every duration is zero (the reference fails downstream on an empty sequence)")
     lib = _lib.lib()
-    ws = torch.empty(lib.parrot_length_regulator_workspace_bytes(B, S, D, L), dtype=torch.uint8, device=seq.device)
+    ws = _workspace(lib.parrot_length_regulator_workspace_bytes(B, S, D, L), seq.device)
     out = torch.empty((B, L, D), dtype=torch.float32, device=seq.device)
     mask = torch.empty((B, L), dtype=torch.uint8, device=seq.device)
     lens = torch.empty((B,), dtype=torch.int32, device=seq.device)
@@ -179,7 +186,7 @@ def debug_attention(qkv: torch.Tensor, valid: torch.Tensor, heads: int, core: in
         out = torch.empty((B, D, T), device=qkv.device, dtype=torch.float32)
     assert out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (B, D, T)
     lib = _lib.lib()
-    ws = torch.empty(lib.parrot_debug_attention_workspace_bytes(B, T, heads, int(core)), dtype=torch.uint8, device=qkv.device)
+    ws = _workspace(lib.parrot_debug_attention_workspace_bytes(B, T, heads, int(core)), qkv.device)
     with torch.cuda.device(qkv.device):
         _lib.check(lib.parrot_debug_attention(dptr(qkv), dptr(valid), dptr(out), B, T, heads, D // heads, int(core), dptr(ws), ws.numel(),
                                               stream_ptr(qkv.device)))

@@ -13,27 +13,12 @@ import os
 from typing import Dict, List, Optional
 
 import torch
-import torch.nn as nn
 
 from . import _lib
-from .ops import PREC_BF16X6, PREC_F16X3, PREC_STR, dptr, param_fingerprint, range_fallback_default, require_cuda, stream_ptr
+from ._handle import RangeFallbackModule, _attach
+from ._lib import ST_NONFINITE
+from .ops import _prec_arg, _workspace, dptr, require_cuda, stream_ptr
 from .synth import sinusoid_table
-
-
-
-def _attach(root: nn.Module, dotted: str, tensor: torch.Tensor, buffer: bool = False) -> None:
-    """Register ``tensor`` under a dotted state_dict key, creating plain container modules on the way
-    (numeric path parts are fine: nn.Module accepts '0' as a child name, as ModuleList does)."""
-    parts = dotted.split(".")
-    m = root
-    for p in parts[:-1]:
-        if p not in m._modules:
-            m.add_module(p, nn.Module())
-        m = m._modules[p]
-    if buffer:
-        m.register_buffer(parts[-1], tensor)
-    else:
-        m.register_parameter(parts[-1], nn.Parameter(tensor))
 
 
 def parrot_param_shapes(cfg: dict, vocab: int, n_speaker: int) -> Dict[str, tuple]:
@@ -73,7 +58,12 @@ def parrot_param_shapes(cfg: dict, vocab: int, n_speaker: int) -> Dict[str, tupl
     return sh
 
 
-class Parrot(nn.Module):
+class Parrot(RangeFallbackModule):
+    # (range-safe fallback: the first decode of every new handle is checked synchronously; non-finite logits under the default
+    # fp16x3 scheme rebuild the handle in bf16x6 and re-run the batch, with a warning)
+    _destroy_fn, _precision_fn = "parrot_tte_destroy", "parrot_tte_precision"
+    _peek_fn, _status_fn, _warn_name = "parrot_tte_status_peek_async", "parrot_tte_status_async", "TTE"
+
     def __init__(self, data_config, src_vocab_size, src_pad_idx):
         super().__init__()
         tr = data_config["transformer"]
@@ -98,54 +88,9 @@ class Parrot(nn.Module):
                     fan_in *= s
                 t = torch.randn(shape, generator=gen) / max(fan_in, 1) ** 0.5
             _attach(self, key, t)
-        self._handle: Optional[C.c_void_p] = None
-        self._handle_device = None
-        self._handle_fp = None
-        # range-safe fallback (see CodeGenerator): the first decode of every new handle is checked synchronously; non-finite logits
-        # under the default fp16x3 scheme rebuild the handle in bf16x6 and re-run the batch, with a warning
-        self.range_fallback = range_fallback_default()
-        self._precision_override: Optional[int] = None
         self._merge_override: Optional[bool] = None  # None: library default (merged); tests build unmerged handles beside it
-        self._probe_pending = False
-        # torch's load_state_dict recurses through _load_from_state_dict and never calls a CHILD's load_state_dict
-        # override, so a reload through any wrapper (LitParrot, nn.Sequential ...) is caught here: the post hook runs
-        # for every module of the tree, and _current_handle() also compares the parameters' version fingerprint.
-        self._fell_back = False  # the override above was set by the range-safe fallback (not by the caller)
-        self.register_load_state_dict_post_hook(lambda module, incompatible: module._on_load())
 
-    # ---- parameter bookkeeping ----------------------------------------------------------------
-    def _on_load(self):
-        """New weights: drop the packed handle -- and a bf16x6 override that the range-safe fallback set for the OLD weights (the new
-        checkpoint gets the default scheme and its own first-forward probe)."""
-        self._invalidate()
-        if self._fell_back:
-            self._precision_override, self._fell_back = None, False
-
-    def _invalidate(self):
-        if self._handle is not None:
-            _lib.lib().parrot_tte_destroy(self._handle)
-        self._handle = None
-
-    def _current_handle(self, dev):
-        """The packed-weight handle for ``dev``, rebuilt when any parameter was replaced, moved or written in place."""
-        fp = param_fingerprint(self)
-        if self._handle is None or self._handle_device != dev or self._handle_fp != fp:
-            self._invalidate()
-            self._build(dev)
-            self._handle_fp = fp
-        return self._handle
-
-    def _apply(self, fn, recurse=True):
-        self._invalidate()
-        return super()._apply(fn, recurse)
-
-    def __del__(self):
-        try:
-            self._invalidate()
-        except Exception:
-            pass
-
-    # ---- HIP handle ---------------------------------------------------------------------------
+    # ---- HIP handle (lifecycle and range-safe fallback: _handle.py) ----------------------------
     def _build(self, device):
         cfgd = self.data_config
         tr, dp = cfgd["transformer"], cfgd["duration_predictor"]
@@ -178,30 +123,10 @@ class Parrot(nn.Module):
         w.head_w, w.head_b = P("head.weight"), P("head.bias")
         hdl = C.c_void_p()
         with torch.cuda.device(device):
-            _lib.check(_lib.lib().parrot_tte_create_ex(C.byref(hdl), C.byref(cfg), C.byref(w),
-                                                       -1 if self._precision_override is None else self._precision_override,
+            _lib.check(_lib.lib().parrot_tte_create_ex(C.byref(hdl), C.byref(cfg), C.byref(w), _prec_arg(self._precision_override),
                                                        -1 if self._merge_override is None else int(self._merge_override)))
         self._handle, self._handle_device = hdl, device
         self._probe_pending = True
-
-    @property
-    def precision_in_use(self) -> Optional[str]:
-        """Precision of the live handle ("f16x3", "bf16x6", ...; None before the first forward)."""
-        if self._handle is None:
-            return None
-        return PREC_STR.get(int(_lib.lib().parrot_tte_precision(self._handle)))
-
-    def _fall_back(self, why: str) -> bool:
-        import warnings
-        cur = None if self._handle is None else int(_lib.lib().parrot_tte_precision(self._handle))
-        if not self.range_fallback or cur != PREC_F16X3:
-            return False
-        warnings.warn(f"parrot_tts_amd TTE: {why}: an activation left the fp16x3 scheme's range (|x| < 8190); rebuilding the handle in "
-                      "bf16x6 (fp32's range) for this and all later batches.", RuntimeWarning, stacklevel=3)
-        self._precision_override = PREC_BF16X6
-        self._fell_back = True
-        self._invalidate()
-        return True
 
     # ---- forward ------------------------------------------------------------------------------
     @staticmethod
@@ -213,7 +138,7 @@ class Parrot(nn.Module):
             raise RuntimeError("repeats can not be negative")
         if code == 7:
             raise ValueError(f"{who}: row_exact=True durations: a nonzero duration at a padded source position (a row alone has no such token)")
-        if code == 5:
+        if code == ST_NONFINITE:
             raise FloatingPointError(f"{who}: non-finite output (waveform sample / logits) -- an activation left the range of the fp16 split "
                                      "scheme (|x| < 8190); use PARROT_PRECISION=bf16x6 or f32 for this checkpoint")
         raise IndexError(f"{who}: embedding index out of range (code {code})")
@@ -271,7 +196,7 @@ class Parrot(nn.Module):
         st = stream_ptr(dev)
         with torch.cuda.device(dev):
             try:
-                ws = torch.empty(lib.parrot_tte_workspace_bytes(self._handle, B, S, 0), dtype=torch.uint8, device=dev)
+                ws = _workspace(lib.parrot_tte_workspace_bytes(self._handle, B, S, 0), dev)
                 _lib.check(lib.parrot_tte_encode(self._handle, dptr(phones), dptr(valid), dptr(speaker) if speaker is not None else None,
                                                  dptr(src_len) if src_len is not None else None, B, S, dptr(log_dur), dptr(dur), dptr(lens),
                                                  dptr(state), state.numel(), dptr(ws), ws.numel(), st))
@@ -283,18 +208,18 @@ class Parrot(nn.Module):
                 hooked = [h if isinstance(h, tuple) else (h, None) for h in hooked]  # (name, on_nonfinite callback or None)
                 status_h = status.cpu()  # the one host sync the reference also has (duration.py:10)
             except _lib.ParrotHipError as e:
-                self._reraise(e)
+                _lib.reraise(e)
         lens_h = status_h[:B]
         if int(status_h[-2]):
             raise ValueError("row_exact=True needs src_mask to be a right-padded prefix per row (modules/data.py:97-104 pads on the right); "
                              "this mask has a pad inside an utterance or left padding -- run the padded-batch mode (row_exact=False) instead")
         # bad phone / speaker ids of THIS encode (the reference's Embedding IndexError), non-finite logits of the previous
         # decode, and whatever the hooks watch (the previous vocoder forward): raised here, by default, at no extra sync
-        if int(status_h[B]) == 5:
+        if int(status_h[B]) == ST_NONFINITE:
             self._fall_back("a previous decode produced non-finite logits")  # (later batches run in bf16x6; this one is reported)
         self._raise_status(int(status_h[B]), "tte")
         for i, (nm, on_nonfinite) in enumerate(hooked):
-            if int(status_h[B + 1 + i]) == 5 and on_nonfinite is not None:
+            if int(status_h[B + 1 + i]) == ST_NONFINITE and on_nonfinite is not None:
                 on_nonfinite()
             self._raise_status(int(status_h[B + 1 + i]), nm)
         if key_mask is not None:
@@ -308,14 +233,6 @@ class Parrot(nn.Module):
         return {"B": B, "S": S, "L": int(lens_h.max()), "dev": dev, "state": state, "log_dur": log_dur, "dur": dur, "lens": lens_h,
                 "lens_dev": lens, "src_mask": src_mask, "handle": self._handle, "row_exact": bool(row_exact)}
 
-    @staticmethod
-    def _reraise(e):
-        if e.code == -2:  # PARROT_E_RANGE <-> the reference's IndexError (pe[T], Embedding)
-            raise IndexError(str(e)) from None
-        if e.code == -6:  # PARROT_E_NONFINITE (flag raised by an earlier decode)
-            raise FloatingPointError(str(e)) from None
-        raise e
-
     @torch.no_grad()
     def _decode(self, ctx: dict, ids: torch.Tensor, tgt: Optional[torch.Tensor], logits: Optional[torch.Tensor],
                 key_mask: Optional[torch.Tensor] = None) -> None:
@@ -324,7 +241,7 @@ class Parrot(nn.Module):
         The scratch buffer is allocated on the current stream."""
         lib = _lib.lib()
         B, S, L, dev = ctx["B"], ctx["S"], ctx["L"], ctx["dev"]
-        ws = torch.empty(lib.parrot_tte_workspace_bytes(self._handle, B, S, L), dtype=torch.uint8, device=dev)
+        ws = _workspace(lib.parrot_tte_workspace_bytes(self._handle, B, S, L), dev)
         state = ctx["state"]
         state.record_stream(torch.cuda.current_stream(dev))
         with torch.cuda.device(dev):
@@ -338,7 +255,7 @@ class Parrot(nn.Module):
                                                      dptr(logits) if logits is not None else None, dptr(state), state.numel(),
                                                      dptr(ws), ws.numel(), stream_ptr(dev)))
             except _lib.ParrotHipError as e:
-                self._reraise(e)
+                _lib.reraise(e)
 
     @torch.no_grad()
     def _run(self, batch, want_logits: bool, status_hooks=(), row_exact: bool = False, durations=None, key_mask=None):
@@ -346,7 +263,6 @@ class Parrot(nn.Module):
         without, under t < max(sum(dur_b), 1) -- the mask collate builds for an utterance of sum(dur_b) codes (key 0 kept for a row
         of none, which emits nothing) -- and every row emits exactly sum(dur_b) ids."""
         ctx = self._encode(batch, status_hooks, row_exact=row_exact, durations=durations, key_mask=key_mask)
-        lib = _lib.lib()
         B, L, dev = ctx["B"], ctx["L"], ctx["dev"]
         teacher = durations is not None
         if teacher:
@@ -362,18 +278,8 @@ class Parrot(nn.Module):
         # last launch and the vocoder's first
         emitted_dev = ctx["lens_dev"] if (row_exact or teacher) else torch.clamp(ctx["lens_dev"] + 1, max=L)
         self._decode(ctx, ids, tgt, logits, key_mask=km if teacher else None)
-        if self._probe_pending:  # first decode of this handle: one synchronous look at the device flag
-            self._probe_pending = False
-            if self.range_fallback and int(lib.parrot_tte_precision(self._handle)) == PREC_F16X3:
-                flag = torch.zeros(1, dtype=torch.int32, device=dev)
-                with torch.cuda.device(dev):
-                    st = stream_ptr(dev)
-                    _lib.check(lib.parrot_tte_status_peek_async(self._handle, dptr(flag), st))
-                    if int(flag.cpu()) == 5:
-                        _lib.check(lib.parrot_tte_status_async(self._handle, dptr(flag), st))  # handled here: clear it
-                        if self._fall_back("the first decode of this handle produced non-finite logits"):
-                            return self._run(batch, want_logits, status_hooks=(), row_exact=row_exact, durations=durations,
-                                             key_mask=key_mask)
+        if self._first_run_overflowed(dev, "the first decode of this handle produced non-finite logits"):
+            return self._run(batch, want_logits, status_hooks=(), row_exact=row_exact, durations=durations, key_mask=key_mask)
         if teacher:  # the caller's mask (forward), or exactly sum(dur_b) ids per row
             tgt_mask = key_mask.to(dev).bool() if key_mask is not None else torch.arange(L, device=dev)[None, :] < ctx["lens_dev"][:, None]
         elif row_exact:  # a row alone is the longest of its batch: exactly `lens` ids, no extra frame (the device mask keeps one key
@@ -447,11 +353,7 @@ class Parrot(nn.Module):
             try:
                 _lib.check(_lib.lib().parrot_tte_check(self._handle, stream_ptr(self._handle_device)))
             except _lib.ParrotHipError as e:
-                if e.code == -2:
-                    raise IndexError(str(e)) from None
-                if e.code == -6:
-                    raise FloatingPointError(str(e)) from None
-                raise
+                _lib.reraise(e)  # (inherited difference: no switch to bf16x6 on a non-finite flag here; CodeGenerator.check_inputs has one)
 
     def forward(self, batch, inference=False):
         """Reference modules/parrot.py:90-110.  ``inference=True``: predicted durations, the decoder's key mask t <= len (quirk Q2).

@@ -15,7 +15,8 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from .ops import PREC_BF16X6, PREC_F16X3, PREC_STR, dptr, param_fingerprint, range_fallback_default, require_cuda, stream_ptr
+from ._handle import RangeFallbackModule
+from .ops import PREC_BF16X6, _prec_arg, _workspace, dptr, require_cuda, stream_ptr
 
 
 class AttrDict(dict):
@@ -97,7 +98,11 @@ class _ResBlock(nn.Module):
         return list(self.convs)
 
 
-class CodeGenerator(nn.Module):
+class CodeGenerator(RangeFallbackModule):
+    _destroy_fn, _precision_fn = "parrot_voc_destroy", "parrot_voc_precision"
+    _peek_fn, _status_fn, _warn_name = "parrot_voc_status_peek_async", "parrot_voc_status_async", "vocoder"
+    _warn_cost, _warn_hint = ", ~1.5x slower", " CodeGenerator.activation_headroom() shows the per-stage maxima."
+
     def __init__(self, h):
         super().__init__()
         self.h = h
@@ -141,46 +146,12 @@ class CodeGenerator(nn.Module):
         if self.multispkr:
             self.spkr = nn.Embedding(10, self._emb_dim)
 
-        self._handle: Optional[C.c_void_p] = None
-        self._handle_device = None
-        self._handle_fp = None
-        self._ws: Dict[tuple, torch.Tensor] = {}
-        # range-safe fallback: the default fp16x3 scheme needs |activation| < 8190, which no checkpoint format promises.  The FIRST
-        # forward of every new handle is checked synchronously (one sync per handle lifetime); a non-finite result rebuilds the
-        # handle in bf16x6 (fp32's range), re-runs the batch and warns.  Later forwards are covered by the asynchronous flag.
-        self.range_fallback = range_fallback_default()
-        self._precision_override: Optional[int] = None  # PARROT_PREC_* this module's handles are created with (None: library default)
-        self._probe_pending = False
-        # a reload through a parent module never reaches a child's load_state_dict override: invalidate from the post
-        # hook torch runs for every module of the tree, and compare the parameter fingerprint before each forward
-        self._fell_back = False  # the override above was set by the range-safe fallback (not by the caller)
-        self.register_load_state_dict_post_hook(lambda module, incompatible: module._on_load())
+        self._ws: Dict[tuple, torch.Tensor] = {}  # the workspace of the last shape, sized by the live handle
 
-    # ---- parameter bookkeeping ----------------------------------------------------------------
-    def _on_load(self):
-        """New weights: drop the packed handle -- and a bf16x6 override that the range-safe fallback set for the OLD weights (the new
-        checkpoint gets the default scheme and its own first-forward probe)."""
-        self._invalidate()
-        if self._fell_back:
-            self._precision_override, self._fell_back = None, False
-
+    # ---- parameter bookkeeping (lifecycle and range-safe fallback: _handle.py) -----------------
     def _invalidate(self):
-        if self._handle is not None:
-            _lib.lib().parrot_voc_destroy(self._handle)
-        self._handle, self._ws = None, {}
-
-    def _current_handle(self, dev):
-        """The packed-weight handle for ``dev``, rebuilt when any parameter was replaced, moved or written in place."""
-        fp = param_fingerprint(self)
-        if self._handle is None or self._handle_device != dev or self._handle_fp != fp:
-            self._invalidate()
-            self._build(dev)
-            self._handle_fp = fp
-        return self._handle
-
-    def _apply(self, fn, recurse=True):
-        self._invalidate()
-        return super()._apply(fn, recurse)
+        super()._invalidate()
+        self._ws = {}
 
     def remove_weight_norm(self):
         """reference models.py:113-119 -- afterwards state_dict() has plain ``weight`` keys."""
@@ -193,12 +164,6 @@ class CodeGenerator(nn.Module):
         for rb in self.resblocks:
             out += rb.ordered()
         return out + [self.conv_post]
-
-    def __del__(self):
-        try:
-            self._invalidate()
-        except Exception:
-            pass
 
     # ---- HIP handle ---------------------------------------------------------------------------
     def _build(self, device, fused=None, debug_handle=False):
@@ -239,54 +204,12 @@ class CodeGenerator(nn.Module):
         w.conv_post_w, w.conv_post_b = host(self.conv_post.folded()), host(self.conv_post.bias)
         hdl = C.c_void_p()
         with torch.cuda.device(device):
-            _lib.check(_lib.lib().parrot_voc_create_ex(C.byref(hdl), C.byref(cfg), C.byref(w),
-                                                       -1 if self._precision_override is None else self._precision_override,
+            _lib.check(_lib.lib().parrot_voc_create_ex(C.byref(hdl), C.byref(cfg), C.byref(w), _prec_arg(self._precision_override),
                                                        -1 if fused is None else int(fused)))
         if debug_handle:
             return hdl
         self._handle, self._handle_device = hdl, device
         self._probe_pending = True
-
-    @property
-    def precision_in_use(self) -> Optional[str]:
-        """Precision of the live handle ("f16x3", "bf16x6", ...; None before the first forward): "bf16x6" after the range-safe
-        fallback replaced a default-precision handle."""
-        if self._handle is None:
-            return None
-        return PREC_STR.get(int(_lib.lib().parrot_voc_precision(self._handle)))
-
-    def _first_forward_overflowed(self, dev) -> bool:
-        """After the FIRST forward of a handle: one synchronous look at the device flag; True = the handle was replaced by a
-        bf16x6 one and the caller re-runs its batch.  (A bad-id flag stays set for check_inputs() / the status hook.)"""
-        if not self._probe_pending:
-            return False
-        self._probe_pending = False
-        if not self.range_fallback:
-            return False
-        flag = torch.zeros(1, dtype=torch.int32, device=dev)
-        lib = _lib.lib()
-        with torch.cuda.device(dev):
-            _lib.check(lib.parrot_voc_status_peek_async(self._handle, dptr(flag), stream_ptr(dev)))
-        if int(flag.cpu()) != 5 or int(lib.parrot_voc_precision(self._handle)) != PREC_F16X3:
-            return False  # (a bad-id flag, or a non-finite result with nothing to fall back to, stays set for check_inputs() / the hook)
-        with torch.cuda.device(dev):
-            _lib.check(lib.parrot_voc_status_async(self._handle, dptr(flag), stream_ptr(dev)))  # handled here: clear it
-        return self._fall_back("the first forward of this handle produced a non-finite waveform")
-
-    def _fall_back(self, why: str) -> bool:
-        """Switch this module to bf16x6 handles after a non-finite result under an fp16 scheme.  Returns False when there is
-        nothing to fall back to (already fp32-range, or the fallback is switched off)."""
-        import warnings
-        cur = None if self._handle is None else int(_lib.lib().parrot_voc_precision(self._handle))
-        if not self.range_fallback or cur not in (PREC_F16X3,):
-            return False
-        warnings.warn(f"parrot_tts_amd vocoder: {why}: an activation left the fp16x3 scheme's range (|x| < 8190); rebuilding the handle "
-                      "in bf16x6 (fp32's range, ~1.5x slower) for this and all later batches. CodeGenerator.activation_headroom() "
-                      "shows the per-stage maxima.", RuntimeWarning, stacklevel=3)
-        self._precision_override = PREC_BF16X6
-        self._fell_back = True
-        self._invalidate()
-        return True
 
     @property
     def upsample_factor(self) -> int:
@@ -355,7 +278,7 @@ class CodeGenerator(nn.Module):
         lib = _lib.lib()
         key = (B, U)
         if key not in self._ws:
-            self._ws = {key: torch.empty(lib.parrot_voc_workspace_bytes(self._handle, B, U), dtype=torch.uint8, device=dev)}
+            self._ws = {key: _workspace(lib.parrot_voc_workspace_bytes(self._handle, B, U), dev)}
         ws = self._ws[key]
         if out is not None:
             if out.shape != (B, 1, self.out_samples(U)) or out.dtype != torch.float32 or out.device != dev or not out.is_contiguous():
@@ -378,7 +301,7 @@ class CodeGenerator(nn.Module):
         with torch.cuda.device(dev):
             _lib.check(lib.parrot_voc_forward_feats(self._handle, dptr(code), dptr(spkr), dptr(feats), n_feat, dptr(lens32), B, U,
                                                     dptr(wav), stage_ptrs, dptr(ws), ws.numel(), stream_ptr(dev)))
-        if self._first_forward_overflowed(dev):
+        if self._first_run_overflowed(dev, "the first forward of this handle produced a non-finite waveform"):
             return self.forward(stages=stages, unit_lens=unit_lens, out=out, **kwargs)
         if _CHECK_FINITE and not bool(torch.isfinite(wav).all()):
             # the default fp16x3 scheme needs |activation| < 8190 (include/parrot_hip.h): beyond that the output is inf/NaN
@@ -426,7 +349,7 @@ class CodeGenerator(nn.Module):
             B, U = code.shape
             n_groups = len(self._rates) + 2
             amax = torch.zeros(n_groups, dtype=torch.float32, device=dev)
-            ws = torch.empty(lib.parrot_voc_workspace_bytes(hdl, B, U), dtype=torch.uint8, device=dev)
+            ws = _workspace(lib.parrot_voc_workspace_bytes(hdl, B, U), dev)
             wav = torch.empty((B, 1, self.out_samples(U)), dtype=torch.float32, device=dev)
             with torch.cuda.device(dev):
                 _lib.check(lib.parrot_voc_debug_absmax(hdl, dptr(amax)))
@@ -482,13 +405,13 @@ class CodeGenerator(nn.Module):
             lib = _lib.lib()
             key = ("chunked", B, int(chunk_units), halo)
             if key not in self._ws:
-                self._ws = {key: torch.empty(lib.parrot_voc_chunked_workspace_bytes(self._handle, B, int(chunk_units), halo), dtype=torch.uint8, device=dev)}
+                self._ws = {key: _workspace(lib.parrot_voc_chunked_workspace_bytes(self._handle, B, int(chunk_units), halo), dev)}
             ws = self._ws[key]
             wav = torch.empty((B, 1, U * self.upsample_factor), dtype=torch.float32, device=dev)
             with torch.cuda.device(dev):
                 _lib.check(lib.parrot_voc_forward_chunked(self._handle, dptr(code), dptr(spkr), dptr(lens32), B, U, int(chunk_units), halo,
                                                           dptr(wav), dptr(ws), ws.numel(), stream_ptr(dev)))
-            if self._first_forward_overflowed(dev):
+            if self._first_run_overflowed(dev, "the first forward of this handle produced a non-finite waveform"):
                 return self.forward_chunked(chunk_units=chunk_units, halo_units=halo_units, unit_lens=unit_lens, **kwargs)
             return wav
         out = torch.empty((code.shape[0], 1, code.shape[1] * self.upsample_factor), dtype=torch.float32, device=code.device)
@@ -521,12 +444,9 @@ class CodeGenerator(nn.Module):
             try:
                 _lib.check(_lib.lib().parrot_voc_check(self._handle, stream_ptr(self._handle_device)))
             except _lib.ParrotHipError as e:
-                if e.code == -2:
-                    raise IndexError(str(e)) from None
-                if e.code == -6:
-                    self._fall_back("an earlier forward produced a non-finite waveform")  # (later forwards run in bf16x6)
-                    raise FloatingPointError(str(e)) from None
-                raise
+                # (inherited difference: a non-finite flag switches later forwards to bf16x6 here; Parrot.check_outputs has no such switch)
+                # (stacklevel 5: past the lambda and reraise, the warning names check_inputs()'s caller, as it always did)
+                _lib.reraise(e, on_nonfinite=lambda: self._fall_back("an earlier forward produced a non-finite waveform", stacklevel=5))
 
 
 def generate(h, generator: CodeGenerator, code: dict):
