@@ -517,6 +517,51 @@ int parrot_ctc_loss_grad(const float* logits, const int64_t* tokens, const int32
                          int32_t T, int32_t V, int32_t N, const double* row_weight /* (B), nullable: all ones */, int32_t zero_infinity,
                          double* nll_out /* (B) */, float* grad_out /* (B, T, V) */, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- the vocoder's adversarial losses (utils/vocoder/models.py:279-310; train.py:141-148, 159-165) ----
+ * feature_loss, generator_loss and discriminator_loss are sums of means over dense fp32 arrays.  One call evaluates a whole
+ * table of such TERMS -- the 54 feature maps and 8 scores of a generator step, say -- with their gradients: one launch reads
+ * every a and b once and writes every requested gradient once, a second one of a single workgroup forms the means.
+ *   PARROT_GAN_L1   mean |a - b|    (one feature_loss term)            grad_b = sgn(b - a) w / n,  grad_a = -grad_b
+ *   PARROT_GAN_SQ1  mean (1 - a)^2  (generator_loss; the real term     grad_a = -2 (1 - a) w / n
+ *                                    of discriminator_loss), b unused
+ *   PARROT_GAN_SQ0  mean a^2        (discriminator_loss's generated    grad_a = 2 a w / n
+ *                                    term), b unused
+ * Each element's contribution is formed in fp64 from the fp32 inputs and summed in fp64 in a fixed order over tiles of
+ * parrot_gan_loss_tile() elements that start at the term's element 0: no atomics, two calls agree bit for bit, and a term's
+ * mean and gradients depend on that term's data, n and weight only -- not on K, on the other terms or on its place in the table.
+ * An L1 gradient element is (float)(w / n) with the sign of the COMPARISON of a and b (exactly 0 where a == b, and where either
+ * is NaN, as torch's sgn); a squares gradient element is the fp64 product rounded once.  n = 0: the mean is NaN (torch's mean
+ * of nothing), no gradient element is touched, the other terms are as ever.  NaN / inf inputs propagate; there is no status word.
+ * More than PARROT_GAN_MAX_TERMS terms become several launches inside the call. */
+#define PARROT_GAN_L1 0
+#define PARROT_GAN_SQ1 1
+#define PARROT_GAN_SQ0 2
+#define PARROT_GAN_MAX_TERMS 64 /* terms per launch: the table travels in the kernel arguments */
+#define PARROT_GAN_GRID_CAP 2048 /* workgroups per launch; further tiles are reached by stride */
+typedef struct {
+    const float* a;
+    const float* b; /* PARROT_GAN_L1 only */
+    float* grad_a;  /* nullable: not wanted */
+    float* grad_b;  /* nullable; PARROT_GAN_L1 only */
+    int64_t n;
+    int32_t op;
+    int32_t reserved;
+} parrot_gan_term_t; /* 48 bytes */
+/* elements per tile */
+int32_t parrot_gan_loss_tile(void);
+/* needs no device; 0 for K <= 0 or a term with n < 0.  A function of K and of the number of tiles alone. */
+size_t parrot_gan_loss_workspace_bytes(const parrot_gan_term_t* terms /* host */, int32_t K);
+/* terms: HOST array of K terms with DEVICE pointers inside.  weights: DEVICE, K doubles, the gradient arriving at each term's mean
+ * (a backward needs no host synchronisation); NULL = ones.  term_out (device, K, nullable) <- the unweighted means in fp64;
+ * total (device, 1, nullable) <- (float)(scale * sum_k term_out[k]), summed in fp64 in table order and rounded once; scale enters
+ * nothing else.  With both null (a backward) the call is the one launch and ws may be null; values without any gradient are the
+ * forward alone.  PARROT_E_INVALID, before any HIP call: a null table with K > 0, an unknown op, n < 0, a null a (or b of an L1
+ * term), grad_b on a squares term, a gradient that aliases its term's a or b, neither values nor a gradient requested;
+ * PARROT_E_NOMEM: ws_bytes < parrot_gan_loss_workspace_bytes(terms, K) when values are requested. */
+int parrot_gan_loss(const parrot_gan_term_t* terms, int32_t K, const double* weights /* device, nullable */, double scale,
+                    double* term_out /* device, K, nullable */, float* total /* device, 1, nullable */, void* ws, size_t ws_bytes,
+                    void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -75,6 +75,14 @@ class AlignerWeights(C.Structure):
                [(n, c_float_p * 2) for n in ("w_ih", "w_hh", "b_ih", "b_hh")] + [("lin_w", c_float_p), ("lin_b", c_float_p)]
 
 
+class GanTerm(C.Structure):  # parrot_gan_term_t: 48 bytes
+    _fields_ = [("a", C.c_void_p), ("b", C.c_void_p), ("grad_a", C.c_void_p), ("grad_b", C.c_void_p), ("n", C.c_int64),
+                ("op", C.c_int32), ("reserved", C.c_int32)]
+
+
+GAN_L1, GAN_SQ1, GAN_SQ0 = 0, 1, 2  # PARROT_GAN_* of include/parrot_hip.h
+GAN_MAX_TERMS, GAN_GRID_CAP = 64, 2048  # PARROT_GAN_MAX_TERMS, PARROT_GAN_GRID_CAP
+
 # name -> (restype, argtypes); every symbol include/parrot_hip.h and include/parrot_hip_debug.h declare
 vp, i32, sz, f32 = C.c_void_p, C.c_int32, C.c_size_t, C.c_float
 SIGNATURES = {
@@ -165,6 +173,9 @@ SIGNATURES = {
     "parrot_ctc_loss": (C.c_int, [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, sz, vp]),
     "parrot_ctc_grad_workspace_bytes": (sz, [i32, i32, i32, i32]),
     "parrot_ctc_loss_grad": (C.c_int, [vp, vp, vp, vp, i32, i32, i32, i32, vp, i32, vp, vp, vp, sz, vp]),
+    "parrot_gan_loss_tile": (i32, []),
+    "parrot_gan_loss_workspace_bytes": (sz, [C.POINTER(GanTerm), i32]),
+    "parrot_gan_loss": (C.c_int, [C.POINTER(GanTerm), i32, vp, C.c_double, vp, vp, vp, sz, vp]),
 }
 
 _lib = None
