@@ -21,6 +21,16 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC"]
 # they stay where they are written: conv_split16 128 x 128: 6.88 -> 6.78 ms per step (mean of five same-box A/B pairs, the
 # sign held in four, one tie: at the edge of the run-to-run noise), no spills, nothing else moves.
 TU_FLAGS = {f: ["-mllvm", "-disable-machine-sink"] for f in ("tu_split16.hip", "tu_split16_wide.hip", "tu_split16_xpl.hip")}
+# The units of the split-scheme MFMA kernels (and the attention cores): no SLP vectoriser.  At -O3 it pairs adjacent scalar fp32
+# multiplies / adds / FMAs of the operand conversion, the bias and rescale loops and the epilogues into v_pk_{mul,add,fma}_f32.
+# A wave64 v_mul_f32 already issues at full rate on gfx950, so packing buys no throughput, and a packed fp32 op beside MFMAs
+# costs more issue time than the two scalar ops it replaces (tools/probes/interleave_unpacked.hip measures both).
+# tests/test_isa_unpacked.py holds these kernels to zero packed fp32 arithmetic and zero scratch.
+NO_SLP_UNITS = ("tu_mrf.hip", "tu_mrf_single.hip", "tu_resblock.hip", "tu_split16.hip", "tu_split16_single.hip",
+                "tu_split16_single_f16.hip", "tu_split16_wide.hip", "tu_split16_xpl.hip", "tu_split_bf16x6.hip", "tu_split_f16x3.hip",
+                "tu_split_single.hip", "tu_attn.hip")
+for _f in NO_SLP_UNITS:
+    TU_FLAGS[_f] = TU_FLAGS.get(_f, []) + ["-fno-slp-vectorize"]
 
 
 def _stale() -> bool:

@@ -27,6 +27,7 @@
 #include <algorithm>
 
 #include "conv_consts.h"
+#include "div_uniform.h"
 
 namespace parrot {
 
@@ -246,6 +247,7 @@ __device__ __forceinline__ void conv_epilogue(const ConvParams& p, f32x16 (&acc)
     const bool late_res = rb != nullptr && !fold_res;
     const bool has_acc = p.epi != EPI_STORE;
     const bool do_div = p.epi == EPI_ADD_DIV;
+    const DivUniform dv = div_uniform(p.div);  // (div_uniform.h: the quotient's bits without the division sequence for d = 3)
     const float act_lo = (p.act == ACT_RELU) ? 0.f : -INFINITY;
 #pragma unroll
     for (int mt = 0; mt < WM; ++mt) {
@@ -277,10 +279,7 @@ __device__ __forceinline__ void conv_epilogue(const ConvParams& p, f32x16 (&acc)
                 float v[8];
 #pragma unroll
                 for (int q = 0; q < 8; ++q) v[q] = yv[q] + (fmaxf(acc[mt][nt][g * 8 + q], act_lo) + rv[q]);
-                if (do_div) {
-#pragma unroll
-                    for (int q = 0; q < 8; ++q) v[q] = v[q] / p.div;
-                }
+                if (do_div) div_rows(dv, v);
 #pragma unroll
                 for (int q = 0; q < 8; ++q)
                     if (off[q] >= 0) yb[off[q]] = v[q];
@@ -371,6 +370,7 @@ __device__ __forceinline__ void conv_epilogue_lean(const ConvParams& p, f32x16 (
     const bool late_res = rb != nullptr && !fold_res;
     const bool has_acc = p.epi != EPI_STORE;
     const bool do_div = p.epi == EPI_ADD_DIV;
+    const DivUniform dv = div_uniform(p.div);  // (div_uniform.h: the quotient's bits without the division sequence for d = 3)
     const bool relu = p.act == ACT_RELU;
     const int row_bytes = p.Tout * 4;
     int vo[WN];
@@ -405,10 +405,7 @@ __device__ __forceinline__ void conv_epilogue_lean(const ConvParams& p, f32x16 (
                 for (int r = 0; r < 16; ++r) yv[r] = row_tile_load(yt, vo[nt], (m0 + (r & 3) + 8 * (r >> 2)) * row_bytes);
 #pragma unroll
                 for (int r = 0; r < 16; ++r) v[r] = yv[r] + v[r];
-                if (do_div) {
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) v[r] = v[r] / p.div;
-                }
+                if (do_div) div_rows(dv, v);
             }
 #pragma unroll
             for (int r = 0; r < 16; ++r) row_tile_store(yt, v[r], vo[nt], (m0 + (r & 3) + 8 * (r >> 2)) * row_bytes);

@@ -142,6 +142,7 @@ __global__ __launch_bounds__(256, MINW) void conv_mfma16_kernel(const ConvParams
     const bool late_res = rb != nullptr && !fold_res;
     const bool has_acc = p.epi != EPI_STORE;
     const bool do_div = p.epi == EPI_ADD_DIV;
+    const DivUniform dv = div_uniform(p.div);
     const float act_lo = (p.act == ACT_RELU) ? 0.f : -INFINITY;
 #pragma unroll
     for (int nt = 0; nt < NT16; ++nt) {
@@ -165,10 +166,7 @@ __global__ __launch_bounds__(256, MINW) void conv_mfma16_kernel(const ConvParams
         }
 #pragma unroll
         for (int r = 0; r < 4; ++r) v[r] = yv[r] + (fmaxf(acc[nt][r], act_lo) + rv[r]);
-        if (do_div) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) v[r] = v[r] / p.div;
-        }
+        if (do_div) div_rows(dv, v);
 #pragma unroll
         for (int r = 0; r < 4; ++r)
             if (off[r] >= 0) yb[off[r]] = v[r];

@@ -270,6 +270,7 @@ __global__ __launch_bounds__(WAVES_M* WAVES_N * 64, MINW) void conv_split16_kern
     const bool late_res = rb != nullptr;
     const bool has_acc = p.epi != EPI_STORE;
     const bool do_div = p.epi == EPI_ADD_DIV;
+    const DivUniform dv = div_uniform(p.div);
     const bool relu = p.act == ACT_RELU;
     const RowTile yt = row_tile(yb, p.M, p.Tout), rt = row_tile(late_res ? rb : yb, p.M, p.Tout);
     if (p.yplane) {
@@ -387,14 +388,17 @@ __global__ __launch_bounds__(WAVES_M* WAVES_N * 64, MINW) void conv_split16_kern
                     stg[wbase + r * RS + tn * 16] = v;
                 }
 #pragma unroll
-            for (int q = 0; q < TN; ++q) {
-                f32x4 v = *reinterpret_cast<const f32x4*>(stg + lq[q]);
-                if (late_res) v = v + rv[q];
+            for (int q = 0; q < TN; ++q) {  // (element by element: vector adds would be v_pk_add_f32, dearer than two v_add_f32 beside MFMAs)
+                const f32x4 sv = *reinterpret_cast<const f32x4*>(stg + lq[q]);
+                float v[4];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) v[e] = late_res ? sv[e] + rv[q][e] : sv[e];
                 if (has_acc) {
-                    v = yv[q] + v;
-                    if (do_div) v = v / p.div;
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) v[e] = yv[q][e] + v[e];
+                    if (do_div) div_rows(dv, v);
                 }
-                row_tile_store4(yt, v, vq[q], soff);
+                row_tile_store4(yt, f32x4{v[0], v[1], v[2], v[3]}, vq[q], soff);
             }
         }
         return;
@@ -443,9 +447,7 @@ __global__ __launch_bounds__(WAVES_M* WAVES_N * 64, MINW) void conv_split16_kern
                 for (int r = 0; r < 4; ++r) v[tn][r] = yv[tn][r] + v[tn][r];
             if (do_div) {
 #pragma unroll
-                for (int tn = 0; tn < TN; ++tn)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) v[tn][r] = v[tn][r] / p.div;
+                for (int tn = 0; tn < TN; ++tn) div_rows(dv, v[tn]);
             }
         }
 #pragma unroll

@@ -172,6 +172,7 @@ __global__ __launch_bounds__(512, 1) void resblock_fused_kernel(const ResblockPa
 
     // ---- write the central TT columns into the MRF accumulator -------------------------------------------------
     float* __restrict__ yb = p.y + (size_t)b * C * p.T;
+    const DivUniform dv = div_uniform(p.div);
     for (int idx = tid; idx < C * p.TT; idx += 512) {
         const int row = idx / p.TT, c = idx - row * p.TT;
         const int t = tile * p.TT + c;
@@ -179,7 +180,7 @@ __global__ __launch_bounds__(512, 1) void resblock_fused_kernel(const ResblockPa
             float v = cur[row * RS + RB_PAD + p.H + c];
             const size_t o = (size_t)row * p.T + t;
             if (p.epi == EPI_ADD) v = yb[o] + v;
-            else if (p.epi == EPI_ADD_DIV) v = (yb[o] + v) / p.div;
+            else if (p.epi == EPI_ADD_DIV) v = div_apply(dv, yb[o] + v);
             yb[o] = v;
         }
     }
@@ -299,6 +300,7 @@ static __global__ __launch_bounds__(512, 1) void resblock_fused16_kernel(const R
         }
     }
     float* __restrict__ yb = p.y + (size_t)b * C * p.T;
+    const DivUniform dv = div_uniform(p.div);
     for (int idx = tid; idx < C * p.TT; idx += 512) {
         const int row = idx / p.TT, c = idx - row * p.TT;
         const int t = tile * p.TT + c;
@@ -306,7 +308,7 @@ static __global__ __launch_bounds__(512, 1) void resblock_fused16_kernel(const R
             float v = cur[row * RS + RB16_PAD + p.H + c];
             const size_t o = (size_t)row * p.T + t;
             if (p.epi == EPI_ADD) v = yb[o] + v;
-            else if (p.epi == EPI_ADD_DIV) v = (yb[o] + v) / p.div;
+            else if (p.epi == EPI_ADD_DIV) v = div_apply(dv, yb[o] + v);
             yb[o] = v;
         }
     }

@@ -54,6 +54,10 @@ __device__ unsigned long long g_rbs_trace[8 * RBS_TRACE_STAMPS];
 #ifndef RBS_EARLY_INNER
 #define RBS_EARLY_INNER 1
 #endif
+// workgroups per CU the 32-channel pair kernel's register budget is held to (3 = 168 VGPRs; experiment builds: 2 = 256)
+#ifndef RBS_WG_32
+#define RBS_WG_32 3
+#endif
 
 struct ResblockSplitParams {
     const float* x;           // (B, C, T) input of the first pair of this launch (C = 32 or 16: the kernel's)
@@ -98,7 +102,7 @@ constexpr int RBS_W = 384;  // 32-channel window (the 64-channel kernel uses hal
 constexpr int rbs_default_wn(int nch) { return (nch / 2 >= 4) ? 1 : 4 / (nch / 2); }
 template <class SCH, int NCH, int WN = 0, bool MRF = false>
 __global__ __launch_bounds__((NCH / 2) * (WN ? WN : rbs_default_wn(NCH)) * 64,
-                             ((NCH / 2) * (WN ? WN : rbs_default_wn(NCH)) * 64 == 512) ? 1 : (SCH::NP == 3 ? 2 : 3)) void resblock_split_kernel(const ResblockSplitParams p) {
+                             ((NCH / 2) * (WN ? WN : rbs_default_wn(NCH)) * 64 == 512) ? 1 : (SCH::NP == 3 ? 2 : (NCH == 2 ? RBS_WG_32 : 3))) void resblock_split_kernel(const ResblockSplitParams p) {
     constexpr int NPC = SCH::NP, NTERM = SCH::NT, STEP_BYTES = SCH::NP * 1024;
     constexpr int C = 16 * NCH, WAVES_M = NCH / 2, WAVES_N = WN ? WN : rbs_default_wn(NCH), NTW = 3, W = WAVES_N * NTW * 32;
     // (with several row tiles the waves of a column group read each other's channels: 32 channels only)
@@ -128,12 +132,16 @@ __global__ __launch_bounds__((NCH / 2) * (WN ? WN : rbs_default_wn(NCH)) * 64,
     RBS_STAMP();  // 0: start
 #endif
 
-    int col[NTW];   // this lane's window column per tile
+    // this lane's window column in tile 0 (tile nt adds 32 nt) and its 16-byte slot in an operand octet: ONE register each -- every
+    // operand address below is `slot0` plus a compile-time offset (tile, chunk, piece go into the DS instruction's offset field).
+    // Three column registers and the three address registers derived from each were what the 168-VGPR kernels spilled.
+    const int col0 = wn * (NTW * 32) + l31;
+    char* const slot0 = smem_raw + half * OCT_BYTES + col0 * 16;
+    auto colf = [&](int nt) __attribute__((always_inline)) { return col0 + nt * 32; };
     bool tok[NTW];  // ... inside the sequence
 #pragma unroll
     for (int nt = 0; nt < NTW; ++nt) {
-        col[nt] = wn * (NTW * 32) + nt * 32 + l31;
-        const int t = t_base + col[nt];
+        const int t = t_base + colf(nt);
         tok[nt] = t >= 0 && t < Tlim;
     }
 
@@ -147,7 +155,7 @@ __global__ __launch_bounds__((NCH / 2) * (WN ? WN : rbs_default_wn(NCH)) * 64,
         const int row_bytes = p.T * 4;
 #pragma unroll
         for (int nt = 0; nt < NTW; ++nt) {
-            const int voff = tok[nt] ? (t_base + col[nt]) * 4 + 4 * half * row_bytes : (int)0x80000000;  // out of range -> 0
+            const int voff = tok[nt] ? (t_base + colf(nt)) * 4 + 4 * half * row_bytes : (int)0x80000000;  // out of range -> 0
 #pragma unroll
             for (int r = 0; r < 16; ++r)
                 R[nt][r] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(xrsrc, voff, (32 * wm + (r & 3) + 8 * (r >> 2)) * row_bytes, 0));
@@ -173,14 +181,16 @@ __global__ __launch_bounds__((NCH / 2) * (WN ? WN : rbs_default_wn(NCH)) * 64,
                 for (int g = 0; g < 2; ++g)
 #pragma unroll
                     for (int e = 0; e < 2; ++e) {
-                        const f32x2 vv = {v[nt][8 * q + 4 * g + 2 * e], v[nt][8 * q + 4 * g + 2 * e + 1]};
-                        const f32x2 a = (SCH::XS != 1.f) ? vv * mul : vv, bq = vv * m2;  // lrelu(c v) = max(c v, c slope v): packed multiplies
-                        SCH::split(max_nc(a[0], bq[0]), max_nc(a[1], bq[1]), qq[g][e]);
+                        // lrelu(c v) = max(c v, c slope v).  Scalar multiplies on purpose (and no SLP vectoriser on this unit, see
+                        // build.py): a v_pk_mul_f32 beside MFMAs costs more than the two v_mul_f32 it replaces
+                        const float v0 = v[nt][8 * q + 4 * g + 2 * e], v1 = v[nt][8 * q + 4 * g + 2 * e + 1];
+                        const float a0 = (SCH::XS != 1.f) ? v0 * mul : v0, a1 = (SCH::XS != 1.f) ? v1 * mul : v1;
+                        SCH::split(max_nc(a0, v0 * m2), max_nc(a1, v1 * m2), qq[g][e]);
                     }
                 // A lane holds 4 of the 8 channels of both octets of this column (the other 4 sit in lane ^ 32).  Swap the
                 // halves across the two half-waves (v_permlane32_swap): lane (col, half h) then owns octet h completely and
                 // stores 16 contiguous bytes -- 8-byte stores at a 32-byte lane stride cost 4.7 -> 4.1 ms in bank conflicts.
-                char* dst = smem_raw + (2 * wm + q) * CH_BYTES + half * OCT_BYTES + col[nt] * 16;
+                char* dst = slot0 + (2 * wm + q) * CH_BYTES + nt * 512;
 #pragma unroll
                 for (int pc = 0; pc < NPC; ++pc) {
                     const auto r0 = __builtin_amdgcn_permlane32_swap(qq[0][0][pc], qq[1][0][pc], false, false);
@@ -200,7 +210,7 @@ __global__ __launch_bounds__((NCH / 2) * (WN ? WN : rbs_default_wn(NCH)) * 64,
                     for (int q = 0; q < 2; ++q)
 #pragma unroll
                         for (int pc = 0; pc < NPC; ++pc)
-                            *reinterpret_cast<uint4*>(smem_raw + (2 * wm + q) * CH_BYTES + half * OCT_BYTES + col[nt] * 16 + pc * PIECE_BYTES) = uint4{0u, 0u, 0u, 0u};
+                            *reinterpret_cast<uint4*>(slot0 + (2 * wm + q) * CH_BYTES + nt * 512 + pc * PIECE_BYTES) = uint4{0u, 0u, 0u, 0u};
                 }
         }
     };
@@ -237,7 +247,7 @@ __global__ __launch_bounds__((NCH / 2) * (WN ? WN : rbs_default_wn(NCH)) * 64,
 #pragma unroll
         for (int nt = 0; nt < NTW; ++nt) {
             // (unclamped: columns outside [0, W) are read only for output columns that are invalid anyway; LDS never faults)
-            const char* src = smem_raw + ch * CH_BYTES + half * OCT_BYTES + (col[nt] + shift) * 16;
+            const char* src = slot0 + shift * 16 + ch * CH_BYTES + nt * 512;
 #pragma unroll
             for (int pc = 0; pc < NPC; ++pc) bb[nt][pc] = *reinterpret_cast<const s16x8*>(src + pc * PIECE_BYTES);
         }
@@ -320,7 +330,7 @@ __global__ __launch_bounds__((NCH / 2) * (WN ? WN : rbs_default_wn(NCH)) * 64,
     // R is carried in SCALED form between pairs: after a pair's second conv the accumulator IS the new residual times rs = XS * wsc
     // of that conv, and it stays in its registers -- the next second conv starts from fma(R, s2 / rs, b2 * s2) in place, the operand
     // conversion takes XS / rs as its factor.  Every factor is a power of two, so each value equals the unscaled formulation's
-    // ((b2 + R) * s2, R = acc / s2) bit for bit; per pair it saves 24 packed multiplies and 24 packed adds of ~560 VALU instructions.
+    // ((b2 + R) * s2, R = acc / s2) bit for bit; per pair it saves 48 multiplies and 48 adds of ~560 VALU instructions.
     float rs = 1.f;  // scale of R (1 after the load)
     for (int mm = 0; mm < p.n_conv; mm += 2) {
         const int m = br * p.n_conv + mm;  // (pair kernels: one branch, m = mm)
@@ -402,26 +412,25 @@ __global__ __launch_bounds__((NCH / 2) * (WN ? WN : rbs_default_wn(NCH)) * 64,
     const int row_bytes = p.T * 4;
     const bool has_acc = !MRF && p.epi != EPI_STORE;
     const bool do_div = p.epi == EPI_ADD_DIV;
+    const DivUniform dv = div_uniform(p.div);  // the branch mean: bit for bit the division, without its instruction sequence for d = 3
 #pragma unroll
     for (int nt = 0; nt < NTW; ++nt) {
-        const int c = col[nt] - p.H;
+        const int c = colf(nt) - p.H;
         const int t = tile * p.TT + c;
         const bool ok = c >= 0 && c < p.TT && t < p.T;
         const int voff = ok ? (4 * half * p.T + t) * 4 : (int)0x80000000;
         float v[16];
         if constexpr (MRF) {
 #pragma unroll
-            for (int r = 0; r < 16; ++r) v[r] = (n_branch > 1) ? XSr[nt][r] / p.div : XSr[nt][r];
+            for (int r = 0; r < 16; ++r) v[r] = XSr[nt][r];
+            if (n_branch > 1) div_rows(dv, v);
         } else if (has_acc) {
             float yv[16];
 #pragma unroll
             for (int r = 0; r < 16; ++r) yv[r] = row_tile_load(yt, voff, (32 * wm + (r & 3) + 8 * (r >> 2)) * row_bytes);
 #pragma unroll
             for (int r = 0; r < 16; ++r) v[r] = yv[r] + R[nt][r];
-            if (do_div) {
-#pragma unroll
-                for (int r = 0; r < 16; ++r) v[r] = v[r] / p.div;
-            }
+            if (do_div) div_rows(dv, v);
         } else {
 #pragma unroll
             for (int r = 0; r < 16; ++r) v[r] = 0.f + R[nt][r];  // (as the accumulating form with y = 0: -0 comes out as +0 in both)
@@ -497,9 +506,9 @@ __global__ __launch_bounds__(256, SCH::NP == 3 ? 2 : 3) void resblock16_split_ke
             for (int u = 0; u < 2; ++u) {
 #pragma unroll
                 for (int e = 0; e < 2; ++e) {
-                    const f32x2 vv = {v[np + u][2 * e], v[np + u][2 * e + 1]};
-                    const f32x2 a = (SCH::XS != 1.f) ? vv * mul : vv, bq = vv * m2;
-                    SCH::split(max_nc(a[0], bq[0]), max_nc(a[1], bq[1]), qq[u][e]);
+                    const float v0 = v[np + u][2 * e], v1 = v[np + u][2 * e + 1];  // (scalar multiplies: see resblock_split_kernel)
+                    const float a0 = (SCH::XS != 1.f) ? v0 * mul : v0, a1 = (SCH::XS != 1.f) ? v1 * mul : v1;
+                    SCH::split(max_nc(a0, v0 * m2), max_nc(a1, v1 * m2), qq[u][e]);
                 }
             }
             // a lane holds 4 of the 8 channels of an octet (the other 4 sit in lane ^ 16): v_permlane16_swap gives the even
@@ -646,6 +655,7 @@ __global__ __launch_bounds__(256, SCH::NP == 3 ? 2 : 3) void resblock16_split_ke
     const int row_bytes = p.T * 4;
     const bool has_acc = p.epi != EPI_STORE;
     const bool do_div = p.epi == EPI_ADD_DIV;
+    const DivUniform dv = div_uniform(p.div);
     if (has_acc) {
 #pragma unroll
         for (int n0 = 0; n0 < NT; n0 += 4) {  // four column tiles per batch: 16 loads in flight
@@ -660,13 +670,14 @@ __global__ __launch_bounds__(256, SCH::NP == 3 ? 2 : 3) void resblock16_split_ke
                 for (int r = 0; r < 4; ++r) yv[i][r] = row_tile_load(yt, voff[i], r * row_bytes);
             }
 #pragma unroll
-            for (int i = 0; i < 4; ++i)
+            for (int i = 0; i < 4; ++i) {
+                float v[4];
 #pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    float v = yv[i][r] + R[n0 + i][r];
-                    if (do_div) v = v / p.div;
-                    row_tile_store(yt, v, voff[i], r * row_bytes);
-                }
+                for (int r = 0; r < 4; ++r) v[r] = yv[i][r] + R[n0 + i][r];
+                if (do_div) div_rows(dv, v);
+#pragma unroll
+                for (int r = 0; r < 4; ++r) row_tile_store(yt, v[r], voff[i], r * row_bytes);
+            }
         }
     } else {
 #pragma unroll
