@@ -62,6 +62,33 @@ int parrot_debug_attention(const float* qkv, const uint8_t* valid, float* ctx, i
                            void* ws, size_t ws_bytes, void* stream);
 int parrot_debug_layernorm(const float* x, const float* gamma, const float* beta, float* y, int32_t B, int32_t C, int32_t T,
                            int32_t relu_in, void* stream);
+/* Tests: the TTE's duration, length-regulator and argmax / tie-guard kernels on their own, through the launch code of the model
+ * (csrc/host_tte.hip), on caller-owned DEVICE buffers.  `status` (one device int, never NULL) takes the place of the handle's status
+ * word: 5 a non-finite log-duration of a real token or a non-finite logit, 6 a negative duration, 7 a duration at s >= src_len.
+ * Null or empty arguments: PARROT_E_INVALID; more than 65535 rows or a dimension beyond PARROT_DEBUG_MAX_DIM: PARROT_E_UNSUPPORTED;
+ * all before any launch.
+ * parrot_debug_durations: duration_kernel -- log_dur (B, S) = ld_raw where the token is real (src_valid (B, S) u8 non-zero, or --
+ *   src_len (B) given -- s < src_len[b]) and 0 elsewhere; dur i64 = max(rint(exp(log_dur) - 1), 0); cum (B, S) i32 its inclusive
+ *   prefix sums and out_len (B) the row sums, both saturated at INT32_MAX.
+ * parrot_debug_length_regulate: dur_prefix_kernel, then length_regulate_kernel, no transposes -- enc (B, D, S) channel-first,
+ *   dur (B, S) i64, src_len nullable, pe (P, D); y (B, D, L) = pe[L] (row_exact: pe[min(len_b, L)]) + the expanded rows;
+ *   tgt_mask (B, L) u8 nullable: t <= len_b (row_exact: t < max(len_b, 1)).  L <= 0: PARROT_E_INVALID; L >= P: PARROT_E_RANGE.
+ * parrot_debug_argmax_guard: argmax_cf_kernel on logits (B, V, L) -> ids (B, L) i64, and with guard > 0 the tie guard: glist
+ *   (2 x 256 ints, (row0 + b, t) pairs), gstat (4 ints: positions guarded, ids changed, smallest margin as float bits, first list
+ *   entry of this row group).  gstat_start (4 HOST ints, nullable) is what gstat holds before the launch -- a test's second row
+ *   group of a decoder lane: [0] entries already listed, [3] = where this group's start; NULL: {0, 0, +inf, 0}.  guard = 0:
+ *   glist / gstat are not touched.  x (B, D, L) non-NULL: tie_guard_refine_kernel follows -- hwt (D, V), hb (V) nullable, and the
+ *   deep form when f (B, F, L) is given: h (B, D, L), w2t (F, D), b2 (D) nullable; gref (256, V) takes the refined logits. */
+#define PARROT_DEBUG_MAX_DIM (1 << 20)
+int parrot_debug_durations(const float* ld_raw, const uint8_t* src_valid, const int32_t* src_len, int32_t B, int32_t S, float* log_dur,
+                           int64_t* dur, int32_t* cum, int32_t* out_len, int32_t* status, void* stream);
+int parrot_debug_length_regulate(const float* enc, const int64_t* dur, const int32_t* src_len, const float* pe, int32_t B, int32_t S,
+                                 int32_t D, int32_t L, int32_t P, int32_t row_exact, float* y, uint8_t* tgt_mask, int32_t* cum,
+                                 int32_t* out_len, int32_t* status, void* stream);
+int parrot_debug_argmax_guard(const float* logits, int32_t B, int32_t V, int32_t L, float guard, int32_t row0, const float* x, int32_t D,
+                              const float* hwt, const float* hb, const float* f, const float* h, const float* w2t, const float* b2,
+                              int32_t F, const int32_t* gstat_start, int64_t* ids, int32_t* glist, int32_t* gstat, float* gref,
+                              int32_t* status, void* stream);
 /* Stage taps of the aligner: while set, every parrot_aligner_forward copies the activation after the third BatchNorm, channel-first
  * (B, conv_dim, T), to bn3_dev and the LSTM output (B, T, 2 lstm_dim) to lstm_dev (DEVICE buffers; NULL entries are skipped). */
 int parrot_aligner_debug_stages(parrot_aligner_t*, float* bn3_dev, float* lstm_dev);

@@ -142,6 +142,10 @@ SIGNATURES = {
     "parrot_debug_attention_workspace_bytes": (sz, [i32, i32, i32, i32]),
     "parrot_debug_attention": (C.c_int, [vp, vp, vp, i32, i32, i32, i32, i32, vp, sz, vp]),
     "parrot_debug_layernorm": (C.c_int, [vp, vp, vp, vp, i32, i32, i32, i32, vp]),
+    "parrot_debug_durations": (C.c_int, [vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp]),
+    "parrot_debug_length_regulate": (C.c_int, [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp]),
+    "parrot_debug_argmax_guard": (C.c_int, [vp, i32, i32, i32, f32, i32, vp, i32, vp, vp, vp, vp, vp, vp, i32, C.POINTER(i32), vp, vp, vp, vp,
+                                            vp, vp]),
     "parrot_length_regulator_workspace_bytes": (sz, [i32, i32, i32, i32]),
     "parrot_length_regulator": (C.c_int, [vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, sz, vp]),
     "parrot_mel_create": (C.c_int, [C.POINTER(vp), C.POINTER(MelCfg), c_float_p, c_float_p]),

@@ -337,6 +337,47 @@ static int fft_block(const parrot_tte* t, const FftLayer* L, TteScratch& w, floa
     return PARROT_OK;
 }
 
+// The launches of the duration / length-regulator / argmax glue kernels (kernels_misc.h), one helper each: the model paths below and
+// the parrot_debug_* entry points (tests) run the same launch code.
+static int launch_durations(const float* ld_raw, const uint8_t* src_valid, float* log_dur, int64_t* dur, int32_t* cum, int32_t* out_len, int B,
+                            int S, const int32_t* src_len, int* err, hipStream_t s) {
+    hipLaunchKernelGGL(duration_kernel, dim3(B), dim3(256), 0, s, ld_raw, src_valid, log_dur, dur, cum, out_len, S, src_len, err);
+    HIP_TRY(hipGetLastError());
+    return PARROT_OK;
+}
+static int launch_dur_prefix(const int64_t* dur, int32_t* cum, int32_t* out_len, int B, int S, int* err, const int32_t* src_len, hipStream_t s) {
+    hipLaunchKernelGGL(dur_prefix_kernel, dim3(B), dim3(256), 0, s, dur, cum, out_len, S, err, src_len);
+    HIP_TRY(hipGetLastError());
+    return PARROT_OK;
+}
+static int launch_length_regulate(const float* enc, const int32_t* cum, const int32_t* out_len, const float* pe, float* y, uint8_t* tgt_mask, int B,
+                                  int S, int L, int D, int* gstat, int gstat_reset, int row_exact, int pe_stride, hipStream_t s) {
+    hipLaunchKernelGGL(length_regulate_kernel, dim3((L + 63) / 64, B), dim3(256), 0, s, enc, cum, out_len, pe, y, tgt_mask, S, L, D, gstat,
+                       gstat_reset, row_exact, pe_stride);
+    HIP_TRY(hipGetLastError());
+    return PARROT_OK;
+}
+// the tie guard's fp64 re-evaluation (tie_guard_refine_kernel): x == NULL switches it off
+struct RefineArgs {
+    const float *x = nullptr, *hwt = nullptr, *hb = nullptr;                     // (B, D, L), (D, V), (V) nullable
+    const float *f = nullptr, *h = nullptr, *w2t = nullptr, *b2 = nullptr;       // deep form (f != NULL): (B, F, L), (B, D, L), (F, D), (D) nullable
+    int D = 0, F = 0;
+    float* gref = nullptr;
+};
+// argmax + tie guard: gstat = {count, ids changed, min margin (float bits), first list entry of this row group}; glist / gstat NULL: ids only
+static int launch_argmax_guard(const float* logits, int64_t* ids, int B, int V, int L, int* err, float guard, int* glist, int* gstat, int row0,
+                               const RefineArgs& r, hipStream_t s) {
+    hipLaunchKernelGGL(argmax_cf_kernel, dim3((L + 63) / 64, B), dim3(64 * ARGMAX_WAVES), 0, s, logits, ids, V, L, err, guard, glist, gstat, row0);
+    HIP_TRY(hipGetLastError());
+    if (gstat && r.x) {  // re-evaluate the head of the low-margin positions in fp64 (workgroups beyond the count exit at once)
+        const bool deep = r.f != nullptr;
+        hipLaunchKernelGGL(tie_guard_refine_kernel, dim3(TIE_GUARD_MAX), dim3(256), (size_t)(r.D + (deep ? r.F : 0)) * sizeof(double), s, r.x, r.hwt,
+                           r.hb, ids, r.D, V, L, glist, gstat, r.f, r.h, r.w2t, r.b2, r.F, r.gref, row0);
+        HIP_TRY(hipGetLastError());
+    }
+    return PARROT_OK;
+}
+
 // Encode rows [row0, row0 + B) of a batch of Bfull rows: every pointer argument is the GROUP's first row; the group's encoder
 // output / duration prefix sums land in rows row0.. of `state` (sized for Bfull rows).  The encoder works row by row and pe[S] is
 // indexed by the padded length S alone (fft.py:18), so a row's result does not depend on the grouping.
@@ -387,8 +428,7 @@ static int tte_encode_rows(parrot_tte_t* t, const int64_t* phones, const uint8_t
     TRY(conv_launch(t->dp1.get(), w.n, nullptr, w.f, B, S, EPI_STORE, 1.f, s, rows_of(src_len)));
     TRY(layernorm(w.f, t->ln1_w, t->ln1_b, w.n, B, NF, S, 1, s));
     TRY(conv_launch(t->dp_proj.get(), w.n, nullptr, w.o, B, S, EPI_STORE, 1.f, s));  // (B,1,S)
-    hipLaunchKernelGGL(duration_kernel, dim3(B), dim3(256), 0, s, w.o, src_mask, log_dur, dur, st.cum, st.out_len, S, src_len);
-    HIP_TRY(hipGetLastError());
+    TRY(launch_durations(w.o, src_mask, log_dur, dur, st.cum, st.out_len, B, S, src_len, t->err, s));
     HIP_TRY(hipMemcpyAsync(out_lens, st.out_len, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
     return PARROT_OK;
 }
@@ -434,10 +474,9 @@ static int tte_decode_rows(parrot_tte_t* t, int32_t Bfull, int32_t S, int32_t L,
     int* const glist = t->glist ? t->glist + (size_t)lane * 2 * TIE_GUARD_MAX : nullptr;
     float* const gref = t->gref ? t->gref + (size_t)lane * TIE_GUARD_MAX * V : nullptr;
     t->lanes_used = (new_batch ? 0 : t->lanes_used) | (1 << lane);
-    hipLaunchKernelGGL(length_regulate_kernel, dim3((L + 63) / 64, B), dim3(256), 0, s, st.enc_out + (size_t)row0 * D * S, st.cum + (size_t)row0 * S,
-                       st.out_len + row0, t->pe, w.x, tgt_mask, S, L, D, t->guard > 0.f ? gstat : nullptr, guard_restart ? 1 : 0, row_exact ? 1 : 0);
+    TRY(launch_length_regulate(st.enc_out + (size_t)row0 * D * S, st.cum + (size_t)row0 * S, st.out_len + row0, t->pe, w.x, tgt_mask, B, S, L, D,
+                               t->guard > 0.f ? gstat : nullptr, guard_restart ? 1 : 0, row_exact ? 1 : 0, -1, s));
     const uint8_t* const valid = key_mask ? key_mask : tgt_mask;
-    HIP_TRY(hipGetLastError());
     auto dbg = [&](size_t idx, const float* src, size_t n) -> int {
         if (idx < t->dbg_dec.size() && t->dbg_dec[idx])
             HIP_TRY(hipMemcpyAsync(t->dbg_dec[idx] + (size_t)row0 * D * L, src, n * sizeof(float), hipMemcpyDeviceToDevice, s));
@@ -451,19 +490,14 @@ static int tte_decode_rows(parrot_tte_t* t, int32_t Bfull, int32_t S, int32_t L,
     TRY(conv_launch(t->head.get(), w.x, nullptr, w.logits, B, L, EPI_STORE, 1.f, s));
     {   // argmax + tie guard: gstat = {count, ids changed, min margin (float bits)} of this decode
         const bool on = t->guard > 0.f;  // (length_regulate_kernel, the first kernel of this decode, has reset gstat)
-        hipLaunchKernelGGL(argmax_cf_kernel, dim3((L + 63) / 64, B), dim3(64 * ARGMAX_WAVES), 0, s, w.logits, ids, V, L, t->err, t->guard,
-                           on ? glist : nullptr, on ? gstat : nullptr, row0);
-        HIP_TRY(hipGetLastError());
-        if (on) {  // re-evaluate the head of the low-margin positions in fp64 (workgroups beyond the count exit at once)
-            // w.f / w.h still hold the last decoder block's relu(conv1) and x + attn: with them the refinement starts one layer
-            // earlier (conv2 + bias + residual in fp64, then the head); without a decoder block it starts at w.x
-            const bool deep = t->last_w2t != nullptr && !t->dec.empty();
-            const int F = c.n_filter_ffn;
-            hipLaunchKernelGGL(tie_guard_refine_kernel, dim3(TIE_GUARD_MAX), dim3(256), (size_t)(D + (deep ? F : 0)) * sizeof(double), s, w.x,
-                               t->head_w, t->head_b, ids, D, V, L, glist, gstat, deep ? w.f : nullptr, deep ? w.h : nullptr, t->last_w2t,
-                               t->last_b2, F, gref, row0);
-            HIP_TRY(hipGetLastError());
-        }
+        // w.f / w.h still hold the last decoder block's relu(conv1) and x + attn: with them the refinement starts one layer
+        // earlier (conv2 + bias + residual in fp64, then the head); without a decoder block it starts at w.x
+        const bool deep = t->last_w2t != nullptr && !t->dec.empty();
+        RefineArgs r;
+        r.x = w.x; r.hwt = t->head_w; r.hb = t->head_b;
+        r.f = deep ? w.f : nullptr; r.h = deep ? w.h : nullptr; r.w2t = t->last_w2t; r.b2 = t->last_b2;
+        r.D = D; r.F = c.n_filter_ffn; r.gref = gref;
+        TRY(launch_argmax_guard(w.logits, ids, B, V, L, t->err, t->guard, on ? glist : nullptr, on ? gstat : nullptr, row0, r, s));
     }
     if (logits) {
         hipLaunchKernelGGL(transpose_cf_to_cl_kernel, dim3((L + 63) / 64, (V + 63) / 64, B), dim3(256), 0, s, w.logits, logits, V, L);
@@ -493,8 +527,7 @@ extern "C" int parrot_tte_set_durations(parrot_tte_t* t, const int64_t* dur, int
     TteState st = tte_state(t, sa, B, S);
     if (!sa.ok) return fail(PARROT_E_NOMEM, "tte_set_durations: state too small");
     if (poison_word()) TRY(poison(out_lens, (size_t)B * sizeof(int32_t), s));
-    hipLaunchKernelGGL(dur_prefix_kernel, dim3(B), dim3(256), 0, s, dur, st.cum, st.out_len, S, t->err, src_len);
-    HIP_TRY(hipGetLastError());
+    TRY(launch_dur_prefix(dur, st.cum, st.out_len, B, S, t->err, src_len, s));
     HIP_TRY(hipMemcpyAsync(out_lens, st.out_len, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
     return PARROT_OK;
 }
@@ -649,6 +682,78 @@ extern "C" int parrot_debug_layernorm(const float* x, const float* gamma, const 
     return layernorm(x, gamma, beta, y, B, C, T, relu_in != 0, s);
 }
 
+// ---------------------------------------------------------------------------------------------
+// The duration, length-regulator and argmax / tie-guard kernels on their own (tests: include/parrot_hip_debug.h), through the launch
+// helpers the model runs, on caller-owned buffers.  `status` stands in for the handle's device status word.
+// ---------------------------------------------------------------------------------------------
+static int debug_sizes(const char* who, long B, long n1, long n2, long n3) {
+    if (B <= 0 || n1 <= 0 || n2 <= 0 || n3 <= 0) return fail(PARROT_E_INVALID, std::string(who) + ": non-positive size");
+    if (B > 65535 || n1 > PARROT_DEBUG_MAX_DIM || n2 > PARROT_DEBUG_MAX_DIM || n3 > PARROT_DEBUG_MAX_DIM)
+        return fail(PARROT_E_UNSUPPORTED, std::string(who) + ": B > 65535 or a dimension beyond PARROT_DEBUG_MAX_DIM");
+    return PARROT_OK;
+}
+extern "C" int parrot_debug_durations(const float* ld_raw, const uint8_t* src_valid, const int32_t* src_len, int32_t B, int32_t S, float* log_dur,
+                                      int64_t* dur, int32_t* cum, int32_t* out_len, int32_t* status, void* stream) {
+    if (!ld_raw || !src_valid || !log_dur || !dur || !cum || !out_len || !status) return fail(PARROT_E_INVALID, "debug_durations: null argument");
+    TRY(debug_sizes("debug_durations", B, S, 1, 1));
+    hipStream_t s = (hipStream_t)stream;
+    if (poison_word()) {
+        TRY(poison(log_dur, (size_t)B * S * sizeof(float), s));
+        TRY(poison(dur, (size_t)B * S * sizeof(int64_t), s));
+        TRY(poison(cum, (size_t)B * S * sizeof(int32_t), s));
+        TRY(poison(out_len, (size_t)B * sizeof(int32_t), s));
+    }
+    return launch_durations(ld_raw, src_valid, log_dur, dur, cum, out_len, B, S, src_len, status, s);
+}
+extern "C" int parrot_debug_length_regulate(const float* enc, const int64_t* dur, const int32_t* src_len, const float* pe, int32_t B, int32_t S,
+                                            int32_t D, int32_t L, int32_t P, int32_t row_exact, float* y, uint8_t* tgt_mask, int32_t* cum,
+                                            int32_t* out_len, int32_t* status, void* stream) {
+    if (!enc || !dur || !pe || !y || !cum || !out_len || !status) return fail(PARROT_E_INVALID, "debug_length_regulate: null argument");
+    if (L <= 0) return fail(PARROT_E_INVALID, "debug_length_regulate: L must be > 0");
+    TRY(debug_sizes("debug_length_regulate", B, S, D, L));
+    if (L >= P) return fail(PARROT_E_RANGE, "debug_length_regulate: L >= P (pe[L] out of range, fft.py:18)");
+    hipStream_t s = (hipStream_t)stream;
+    if (poison_word()) {
+        TRY(poison(y, (size_t)B * D * L * sizeof(float), s));
+        TRY(poison(tgt_mask, (size_t)B * L, s));
+        TRY(poison(cum, (size_t)B * S * sizeof(int32_t), s));
+        TRY(poison(out_len, (size_t)B * sizeof(int32_t), s));
+    }
+    TRY(launch_dur_prefix(dur, cum, out_len, B, S, status, src_len, s));
+    return launch_length_regulate(enc, cum, out_len, pe, y, tgt_mask, B, S, L, D, nullptr, 1, row_exact ? 1 : 0, -1, s);
+}
+extern "C" int parrot_debug_argmax_guard(const float* logits, int32_t B, int32_t V, int32_t L, float guard, int32_t row0, const float* x, int32_t D,
+                                         const float* hwt, const float* hb, const float* f, const float* h, const float* w2t, const float* b2,
+                                         int32_t F, const int32_t* gstat_start, int64_t* ids, int32_t* glist, int32_t* gstat, float* gref,
+                                         int32_t* status, void* stream) {
+    if (!logits || !ids || !glist || !gstat || !status) return fail(PARROT_E_INVALID, "debug_argmax_guard: null argument");
+    TRY(debug_sizes("debug_argmax_guard", B, V, L, 1));
+    if (!(guard >= 0.f) || row0 < 0) return fail(PARROT_E_INVALID, "debug_argmax_guard: guard and row0 must be >= 0");
+    const bool on = guard > 0.f, deep = f != nullptr;
+    if (x) {
+        if (!hwt || !gref || (deep && (!h || !w2t))) return fail(PARROT_E_INVALID, "debug_argmax_guard: refinement without hwt / gref (deep form: h, w2t)");
+        TRY(debug_sizes("debug_argmax_guard", B, D, deep ? F : 1, 1));
+        if ((size_t)(D + (deep ? F : 0)) * sizeof(double) > 60000) return fail(PARROT_E_UNSUPPORTED, "debug_argmax_guard: D + F doubles beyond the workgroup's LDS");
+    }
+    if (gstat_start && (gstat_start[0] < 0 || gstat_start[3] < 0 || gstat_start[3] > std::min(gstat_start[0], TIE_GUARD_MAX)))
+        return fail(PARROT_E_INVALID, "debug_argmax_guard: gstat_start needs 0 <= [3] <= min([0], 256)");
+    hipStream_t s = (hipStream_t)stream;
+    if (poison_word()) {  // (a preset list is an input: with gstat_start, and with the guard off, list / statistics / refined rows stay the caller's)
+        TRY(poison(ids, (size_t)B * L * sizeof(int64_t), s));
+        if (on && !gstat_start) {
+            TRY(poison(glist, (size_t)2 * TIE_GUARD_MAX * sizeof(int32_t), s));
+            if (x) TRY(poison(gref, (size_t)TIE_GUARD_MAX * V * sizeof(float), s));
+        }
+    }
+    if (on) {  // what length_regulate_kernel leaves at the start of a decode: a restart, or the caller's second row group of a lane
+        const int32_t restart[4] = {0, 0, 0x7f800000, 0};
+        HIP_TRY(hipMemcpyAsync(gstat, gstat_start ? gstat_start : restart, sizeof(restart), hipMemcpyHostToDevice, s));
+    }
+    RefineArgs r;
+    r.x = x; r.hwt = hwt; r.hb = hb; r.f = f; r.h = h; r.w2t = w2t; r.b2 = b2; r.D = D; r.F = F; r.gref = gref;
+    return launch_argmax_guard(logits, ids, B, V, L, status, guard, on ? glist : nullptr, on ? gstat : nullptr, row0, r, s);
+}
+
 extern "C" int parrot_tte_debug_stages(parrot_tte_t* t, float* const* enc_ptrs, float* const* dec_ptrs) {
     if (!t) return fail(PARROT_E_INVALID, "tte_debug_stages: null handle");
     t->dbg_enc.clear();
@@ -695,8 +800,8 @@ extern "C" int parrot_length_regulator(const float* seq, const int64_t* dur, int
     HIP_TRY(hipMemsetAsync(w.zero, 0, (size_t)D * sizeof(float), s));
     // (B,S,D) -> (B,D,S): the transpose kernel with the roles of C and T swapped
     hipLaunchKernelGGL(transpose_cf_to_cl_kernel, dim3((D + 63) / 64, (S + 63) / 64, B), dim3(256), 0, s, seq, w.seq_cf, S, D);
-    hipLaunchKernelGGL(dur_prefix_kernel, dim3(B), dim3(256), 0, s, dur, w.cum, w.lens, S);
-    hipLaunchKernelGGL(length_regulate_kernel, dim3((L + 63) / 64, B), dim3(256), 0, s, w.seq_cf, w.cum, w.lens, w.zero, w.out_cf, mask, S, L, D, nullptr, 1, 0, 0);
+    TRY(launch_dur_prefix(dur, w.cum, w.lens, B, S, nullptr, nullptr, s));
+    TRY(launch_length_regulate(w.seq_cf, w.cum, w.lens, w.zero, w.out_cf, mask, B, S, L, D, nullptr, 1, 0, 0, s));
     hipLaunchKernelGGL(transpose_cf_to_cl_kernel, dim3((L + 63) / 64, (D + 63) / 64, B), dim3(256), 0, s, w.out_cf, out, D, L);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(out_lens, w.lens, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToDevice, s));

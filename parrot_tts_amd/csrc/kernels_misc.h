@@ -165,55 +165,72 @@ static __global__ __launch_bounds__(256) void softmax_mask_kernel(float* __restr
 }
 
 // ---------------------------------------------------------------------------------------------
+// Row sums of durations, shared by duration_kernel and dur_prefix_kernel: int64 sums, stored saturated at INT32_MAX (a single
+// duration is capped at INT32_MAX first, so S of them cannot overflow int64).  A row longer than max_len keeps a length the
+// host's checks see: the decode's L < max_len check then fails as pe[L] does in the reference (fft.py:18).
+// ---------------------------------------------------------------------------------------------
+static __device__ __forceinline__ int32_t sat_i32(int64_t v) { return (int32_t)min(v, (int64_t)INT32_MAX); }
+// The 256 threads' partial sums -> each thread's exclusive prefix (returned); thread 0 stores the row total.  Two barriers.
+static __device__ __forceinline__ int64_t row_prefix_256(int64_t local, int64_t* __restrict__ part, int32_t* __restrict__ row_total) {
+    const int tid = threadIdx.x;
+    part[tid] = local;
+    __syncthreads();
+    if (tid == 0) {
+        int64_t run = 0;
+        for (int i = 0; i < 256; ++i) {
+            const int64_t v = part[i];
+            part[i] = run;
+            run += v;
+        }
+        *row_total = sat_i32(run);
+    }
+    __syncthreads();
+    return part[tid];
+}
+
+// ---------------------------------------------------------------------------------------------
 // Durations (parrot.py:82-86, duration.py:46-47): ld = masked_fill(ld, pad, 0);
 // dur = max(rint(exp(ld) - 1), 0) as int64 (torch.round = round-half-even = rintf);
-// one block per batch row also produces out_len[b] = sum(dur) and the exclusive prefix sums.
+// one block per batch row also produces out_len[b] = sum(dur) and the inclusive prefix sums (row_prefix_256: saturated).
+// A log-duration beyond ln(2^31) is one token longer than any max_len: the int32 sums this kernel once kept wrapped (three
+// tokens of 2^32 + 512 j beside normal ones came out as a plausible short row).  dur itself saturates at INT64_MAX.
+// err (nullable): a REAL token whose log-duration is NaN or +inf raises device status 5 (the reference fails there:
+// "repeats can not be negative" / pe[T] out of range); at a padded position the value is masked to 0 first and changes nothing.
 // ---------------------------------------------------------------------------------------------
 static __global__ __launch_bounds__(256) void duration_kernel(const float* __restrict__ ld_raw, const uint8_t* __restrict__ src_valid,
                                                        float* __restrict__ log_dur, int64_t* __restrict__ dur,
                                                        int32_t* __restrict__ cum /* (B,S) inclusive */, int32_t* __restrict__ out_len,
-                                                       int S, const int32_t* __restrict__ src_len = nullptr) {
-    __shared__ int32_t part[256];
+                                                       int S, const int32_t* __restrict__ src_len = nullptr, int* __restrict__ err = nullptr) {
+    __shared__ int64_t part[256];
     const int b = blockIdx.x, tid = threadIdx.x;
     const int per = (S + 255) / 256;
-    const int s_begin = tid * per, s_end = min(S, s_begin + per);
-    int32_t local = 0;
+    const int s_begin = min(S, tid * per), s_end = min(S, s_begin + per);
+    int64_t local = 0;
     for (int s = s_begin; s < s_end; ++s) {
         // (row-exact: the row's own token count decides, not the key mask -- a row of NO tokens keeps key 0 attendable so that its
         //  softmax is defined, and must still expand to nothing)
         const bool real = src_len ? s < src_len[b] : src_valid[(size_t)b * S + s] != 0;
         float v = real ? ld_raw[(size_t)b * S + s] : 0.0f;
         log_dur[(size_t)b * S + s] = v;
+        if (err && !(v < INFINITY)) atomicExch(err, 5);  // NaN or +inf (-inf is a duration of 0)
         float d = rintf(expf(v) - 1.0f);
         d = d > 0.f ? d : 0.f;
-        const int64_t di = (int64_t)d;
+        const int64_t di = d < 9.2233720e18f ? (int64_t)d : INT64_MAX;
         dur[(size_t)b * S + s] = di;
-        local += (int32_t)di;
+        local += min(di, (int64_t)INT32_MAX);
     }
-    part[tid] = local;
-    __syncthreads();
-    if (tid == 0) {
-        int32_t run = 0;
-        for (int i = 0; i < 256; ++i) {
-            const int32_t v = part[i];
-            part[i] = run;
-            run += v;
-        }
-        out_len[b] = run;
-    }
-    __syncthreads();
-    int32_t run = part[tid];
+    int64_t run = row_prefix_256(local, part, out_len + b);
     for (int s = s_begin; s < s_end; ++s) {
-        run += (int32_t)dur[(size_t)b * S + s];
-        cum[(size_t)b * S + s] = run;
+        run += min(dur[(size_t)b * S + s], (int64_t)INT32_MAX);
+        cum[(size_t)b * S + s] = sat_i32(run);
     }
 }
 
 // inclusive prefix sums + totals of given (B,S) durations: parrot_length_regulator (the standalone entry point) and teacher
 // forcing (parrot_tte_set_durations: parrot.py:104, forward_duration(..., dur_target), duration.py:6-24).  Every position counts,
 // padded ones included (repeat_interleave expands whatever it is given, duration.py:13-14); a negative duration counts as 0.
-// Sums are int64, stored saturated at INT32_MAX: a row longer than max_len keeps its true length for the host's tgt_mask width
-// check (duration.py:12), and the decode's L < max_len check then fails as pe[L] does in the reference (fft.py:18).
+// Sums are int64, stored saturated at INT32_MAX (row_prefix_256): a row longer than max_len keeps its true length for the host's
+// tgt_mask width check (duration.py:12).
 // err (nullable): a negative duration raises device status 6 (torch: "repeats can not be negative"); with src_len (row-exact
 // encode) a nonzero duration at s >= src_len[b] raises 7 (the row alone has no such token) and counts as 0.
 static __global__ __launch_bounds__(256) void dur_prefix_kernel(const int64_t* __restrict__ dur, int32_t* __restrict__ cum, int32_t* __restrict__ out_len, int S,
@@ -237,22 +254,10 @@ static __global__ __launch_bounds__(256) void dur_prefix_kernel(const int64_t* _
     };
     int64_t local = 0;
     for (int s = s_begin; s < s_end; ++s) local += take(s);
-    part[tid] = local;
-    __syncthreads();
-    if (tid == 0) {
-        int64_t run = 0;
-        for (int i = 0; i < 256; ++i) {
-            const int64_t v = part[i];
-            part[i] = run;
-            run += v;
-        }
-        out_len[b] = (int32_t)min(run, (int64_t)INT32_MAX);
-    }
-    __syncthreads();
-    int64_t run = part[tid];
+    int64_t run = row_prefix_256(local, part, out_len + b);
     for (int s = s_begin; s < s_end; ++s) {
         run += take(s);
-        cum[(size_t)b * S + s] = (int32_t)min(run, (int64_t)INT32_MAX);
+        cum[(size_t)b * S + s] = sat_i32(run);
     }
 }
 
@@ -596,8 +601,9 @@ static __global__ __launch_bounds__(64 * ARGMAX_WAVES) void argmax_cf_kernel(con
         if (err && nf) atomicExch(err, 5);  // NaN / inf logits (an activation left the fp16 split range)
         if (gstat) {
             const float margin = m - s2;  // >= 0, or NaN when the column holds non-finite logits (flagged above)
-            if (margin >= 0.f) atomicMin(gstat + 2, __float_as_int(margin));
-            if (!(margin >= guard)) {  // (a NaN margin is guarded too: a non-finite logit never silently skips the re-evaluation)
+            // (sign bit cleared: -0.0 against +0.0 is a tie whose difference can come out as -0.0, which would order below every margin)
+            if (margin >= 0.f) atomicMin(gstat + 2, __float_as_int(margin) & 0x7fffffff);
+            if (!(margin >= guard) || nf) {  // (a NaN margin and a column with any non-finite logit are guarded too: one +inf gives margin +inf)
                 const int slot = atomicAdd(gstat, 1);
                 if (slot < TIE_GUARD_MAX) { glist[2 * slot] = row0 + b; glist[2 * slot + 1] = t; }  // (batch row; b is the row inside this group)
             }

@@ -1,5 +1,5 @@
-"""Thin tensor-level wrappers over the single-op C-ABI entry points (conv plan, int16 cast, selftest, the TTE's attention cores
-and LayerNorm on their own).
+"""Thin tensor-level wrappers over the single-op C-ABI entry points (conv plan, int16 cast, selftest, the TTE's attention cores,
+LayerNorm and duration / length-regulator / argmax kernels on their own).
 
 PyTorch is plumbing only: it owns device memory and the stream; all arithmetic happens in
 libparrot_hip.so."""
@@ -208,4 +208,92 @@ def debug_layernorm(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, re
     with torch.cuda.device(x.device):
         _lib.check(_lib.lib().parrot_debug_layernorm(dptr(x), dptr(gamma), dptr(beta), dptr(out), B, C_, T, int(bool(relu_in)),
                                                      stream_ptr(x.device)))
+    return out
+
+
+TIE_GUARD_MAX = 256  # guarded positions per decoder lane (csrc/kernels_misc.h)
+
+
+def _dev_arg(t: Optional[torch.Tensor], dtype, shape, dev, name: str) -> None:
+    if t is not None:
+        assert t.dtype == dtype and t.is_contiguous() and tuple(t.shape) == tuple(shape) and t.device == dev, name
+
+
+def debug_durations(ld_raw: torch.Tensor, src_valid: torch.Tensor, src_len: Optional[torch.Tensor] = None, out: Optional[dict] = None) -> dict:
+    """duration_kernel on its own (tests; include/parrot_hip_debug.h): ld_raw (B, S) f32, src_valid (B, S) u8, src_len (B) i32 or None
+    -> {"log_dur" (B, S) f32, "dur" (B, S) i64, "cum" (B, S) i32, "out_len" (B) i32, "status" (1) i32}.  ``out``: such a dict of
+    caller-owned tensors to write into (``status`` is then not cleared first)."""
+    require_cuda(ld_raw, "ld_raw")
+    dev = ld_raw.device
+    assert ld_raw.dim() == 2
+    B, S = ld_raw.shape
+    _dev_arg(ld_raw, torch.float32, (B, S), dev, "ld_raw")
+    _dev_arg(src_valid, torch.uint8, (B, S), dev, "src_valid")
+    _dev_arg(src_len, torch.int32, (B,), dev, "src_len")
+    if out is None:
+        out = {"log_dur": torch.empty((B, S), dtype=torch.float32, device=dev), "dur": torch.empty((B, S), dtype=torch.int64, device=dev),
+               "cum": torch.empty((B, S), dtype=torch.int32, device=dev), "out_len": torch.empty((B,), dtype=torch.int32, device=dev),
+               "status": torch.zeros((1,), dtype=torch.int32, device=dev)}
+    for k, (dt, sh) in dict(log_dur=(torch.float32, (B, S)), dur=(torch.int64, (B, S)), cum=(torch.int32, (B, S)),
+                            out_len=(torch.int32, (B,)), status=(torch.int32, (1,))).items():
+        _dev_arg(out[k], dt, sh, dev, k)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().parrot_debug_durations(dptr(ld_raw), dptr(src_valid), dptr(src_len), B, S, dptr(out["log_dur"]), dptr(out["dur"]),
+                                                     dptr(out["cum"]), dptr(out["out_len"]), dptr(out["status"]), stream_ptr(dev)))
+    return out
+
+
+def debug_length_regulate(enc: torch.Tensor, dur: torch.Tensor, pe: torch.Tensor, L: int, row_exact: bool = False,
+                          src_len: Optional[torch.Tensor] = None, want_mask: bool = True, out: Optional[dict] = None) -> dict:
+    """dur_prefix_kernel + length_regulate_kernel on their own (tests): enc (B, D, S) f32 channel-first, dur (B, S) i64, pe (P, D) f32
+    -> {"y" (B, D, L), "tgt_mask" (B, L) u8 or None, "cum" (B, S) i32, "out_len" (B) i32, "status" (1) i32}."""
+    require_cuda(enc, "enc")
+    dev = enc.device
+    assert enc.dim() == 3 and pe.dim() == 2
+    B, D, S = enc.shape
+    P = pe.shape[0]
+    _dev_arg(enc, torch.float32, (B, D, S), dev, "enc")
+    _dev_arg(dur, torch.int64, (B, S), dev, "dur")
+    _dev_arg(pe, torch.float32, (P, D), dev, "pe")
+    _dev_arg(src_len, torch.int32, (B,), dev, "src_len")
+    if out is None:
+        n = max(int(L), 1)
+        out = {"y": torch.empty((B, D, n), dtype=torch.float32, device=dev),
+               "tgt_mask": torch.empty((B, n), dtype=torch.uint8, device=dev) if want_mask else None,
+               "cum": torch.empty((B, S), dtype=torch.int32, device=dev), "out_len": torch.empty((B,), dtype=torch.int32, device=dev),
+               "status": torch.zeros((1,), dtype=torch.int32, device=dev)}
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().parrot_debug_length_regulate(dptr(enc), dptr(dur), dptr(src_len), dptr(pe), B, S, D, int(L), P, int(bool(row_exact)),
+                                                           dptr(out["y"]), dptr(out["tgt_mask"]), dptr(out["cum"]), dptr(out["out_len"]),
+                                                           dptr(out["status"]), stream_ptr(dev)))
+    return out
+
+
+def debug_argmax_guard(logits: torch.Tensor, guard: float, row0: int = 0, refine: Optional[dict] = None, gstat_start=None,
+                       out: Optional[dict] = None) -> dict:
+    """argmax_cf_kernel (+ tie_guard_refine_kernel when ``refine`` is given) on their own (tests): logits (B, V, L) f32 channel-first
+    -> {"ids" (B, L) i64, "glist" (256, 2) i32, "gstat" (4) i32, "gref" (256, V) f32, "status" (1) i32}.  ``refine``: {"x" (B, D, L),
+    "hwt" (D, V), "hb" (V) or None} and for the deep form also {"f" (B, F, L), "h" (B, D, L), "w2t" (F, D), "b2" (D) or None}.
+    ``gstat_start``: four ints, what gstat holds before the launch (NULL: a restart)."""
+    require_cuda(logits, "logits")
+    dev = logits.device
+    assert logits.dim() == 3
+    B, V, L = logits.shape
+    _dev_arg(logits, torch.float32, (B, V, L), dev, "logits")
+    r = dict(refine or {})
+    x, f = r.get("x"), r.get("f")
+    D = int(x.shape[1]) if x is not None else 0
+    F = int(f.shape[1]) if f is not None else 0
+    for k, sh in dict(x=(B, D, L), hwt=(D, V), hb=(V,), f=(B, F, L), h=(B, D, L), w2t=(F, D), b2=(D,)).items():
+        _dev_arg(r.get(k), torch.float32, sh, dev, k)
+    if out is None:
+        out = {"ids": torch.empty((B, L), dtype=torch.int64, device=dev), "glist": torch.zeros((TIE_GUARD_MAX, 2), dtype=torch.int32, device=dev),
+               "gstat": torch.zeros((4,), dtype=torch.int32, device=dev), "gref": torch.zeros((TIE_GUARD_MAX, V), dtype=torch.float32, device=dev),
+               "status": torch.zeros((1,), dtype=torch.int32, device=dev)}
+    start = None if gstat_start is None else (C.c_int32 * 4)(*[int(v) for v in gstat_start])
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().parrot_debug_argmax_guard(dptr(logits), B, V, L, float(guard), int(row0), dptr(x), D, dptr(r.get("hwt")),
+                                                        dptr(r.get("hb")), dptr(f), dptr(r.get("h")), dptr(r.get("w2t")), dptr(r.get("b2")), F,
+                                                        start, dptr(out["ids"]), dptr(out["glist"]), dptr(out["gstat"]), dptr(out["gref"]),
+                                                        dptr(out["status"]), stream_ptr(dev)))
     return out

@@ -228,7 +228,9 @@ class Parrot(RangeFallbackModule):
             if int(status_h[-1]):
                 raise ValueError("tgt_mask has a row with no True entry: the reference's attention gives NaN for that row (torch "
                                  "MultiheadAttention over all-masked keys); every row needs at least one target frame")
-        if durations is not None and int(lens_h.max()) >= self.max_len:  # (before the decode sizes its scratch by L)
+        # (before the decode sizes its scratch by L: predicted durations reach here too -- a log-duration beyond ln(2^31) saturates
+        #  the row's length at INT32_MAX, and a scratch buffer of that many frames must never be asked for)
+        if int(lens_h.max()) >= self.max_len:
             raise IndexError(f"expanded length {int(lens_h.max())} >= max_len {self.max_len} (pe[T] out of range, fft.py:18)")
         return {"B": B, "S": S, "L": int(lens_h.max()), "dev": dev, "state": state, "log_dur": log_dur, "dur": dur, "lens": lens_h,
                 "lens_dev": lens, "src_mask": src_mask, "handle": self._handle, "row_exact": bool(row_exact)}
