@@ -517,6 +517,57 @@ int parrot_ctc_loss_grad(const float* logits, const int64_t* tokens, const int32
                          int32_t T, int32_t V, int32_t N, const double* row_weight /* (B), nullable: all ones */, int32_t zero_infinity,
                          double* nll_out /* (B) */, float* grad_out /* (B, T, V) */, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- training the aligner (utils/aligner/model.py:5-48 under model.train(); trainer.py:60-71) ----
+ * The forward on BATCH statistics and the full backward, as two stateless calls.  Every weight is read from the DEVICE pointer
+ * given here, in torch's layout: nothing is packed, cached or copied to the host, and neither call synchronises, so a parameter an
+ * optimiser has just updated in place is seen by the next call.
+ *   per block: conv(k = 5, pad 2, no bias) -> ReLU -> BatchNorm1d.  training != 0: per channel over all n = B T values of the
+ *   padded batch (nothing is masked), y = (x - mean) rsqrt(var_biased + eps) gamma + beta, and the running buffers are updated
+ *   in place: running_mean <- 0.9 running_mean + 0.1 mean, running_var <- 0.9 running_var + 0.1 var_biased n / (n - 1)
+ *   (num_batches_tracked is the caller's).  training == 0: the running statistics, and no buffer is touched.
+ *   then the bidirectional LSTM (gates i, f, g, o; h_0 = c_0 = 0) and Linear(2 lstm_dim -> num_symbols).
+ * All products are exact fp32 (fp32 MFMA / FMA, fp32 accumulation); the batch statistics and every gradient that sums over B T
+ * (weights, biases, gamma, beta) are summed in fp64 over fixed blocks in a fixed order and rounded once.  No floating-point
+ * atomics: two calls on the same inputs agree bit for bit.  NaN / inf propagate as in torch and nothing is raised.
+ * Limits and argument errors are parrot_aligner_forward's (conv_dim, lstm_dim multiples of 16, lstm_dim <= 1024, T <= 32768),
+ * and B T <= 3 355 392; B T == 1 with training != 0 is PARROT_E_INVALID (torch: "Expected more than 1 value per channel"). */
+typedef struct {
+    const float* conv_w[3];    /* the fields of parrot_aligner_weights, as fp32 DEVICE pointers */
+    const float* bn_weight[3];
+    const float* bn_bias[3];
+    float* bn_mean[3];         /* running_mean / running_var: updated in place by a training forward */
+    float* bn_var[3];
+    const float* w_ih[2];
+    const float* w_hh[2];
+    const float* b_ih[2];
+    const float* b_hh[2];
+    const float* lin_w;
+    const float* lin_b;
+} parrot_aligner_dev_weights;
+/* Where the backward writes d loss / d parameter: device, the parameter's own shape.  A null field is not computed. */
+typedef struct {
+    float* conv_w[3];
+    float* bn_weight[3];
+    float* bn_bias[3];
+    float* w_ih[2];
+    float* w_hh[2];
+    float* b_ih[2];            /* b_ih and b_hh receive the same bits */
+    float* b_hh[2];
+    float* lin_w;
+    float* lin_b;
+} parrot_aligner_grads;
+/* Bytes of what the forward keeps for the backward, and of the workspace of either call (0 beyond the limits). */
+size_t parrot_aligner_train_saved_bytes(const parrot_aligner_cfg* cfg, int32_t B, int32_t T);
+size_t parrot_aligner_train_workspace_bytes(const parrot_aligner_cfg* cfg, int32_t B, int32_t T);
+/* mel (B, T, n_mels) -> logits (B, T, num_symbols).  saved: parrot_aligner_train_saved_bytes, may be NULL when training == 0. */
+int parrot_aligner_train_forward(const parrot_aligner_cfg* cfg, const parrot_aligner_dev_weights* w, const float* mel, int32_t B, int32_t T,
+                                 int32_t training, float* logits, void* saved, void* ws, size_t ws_bytes, void* stream);
+/* The gradients of every parameter from grad_logits (B, T, num_symbols), after a training forward on the same mel, weights and
+ * `saved`.  mel gets no gradient. */
+int parrot_aligner_train_backward(const parrot_aligner_cfg* cfg, const parrot_aligner_dev_weights* w, const float* mel, const void* saved,
+                                  const float* grad_logits, int32_t B, int32_t T, const parrot_aligner_grads* grads, void* ws, size_t ws_bytes,
+                                  void* stream);
+
 /* ---- the vocoder's adversarial losses (utils/vocoder/models.py:279-310; train.py:141-148, 159-165) ----
  * feature_loss, generator_loss and discriminator_loss are sums of means over dense fp32 arrays.  One call evaluates a whole
  * table of such TERMS -- the 54 feature maps and 8 scores of a generator step, say -- with their gradients: one launch reads

@@ -75,6 +75,16 @@ class AlignerWeights(C.Structure):
                [(n, c_float_p * 2) for n in ("w_ih", "w_hh", "b_ih", "b_hh")] + [("lin_w", c_float_p), ("lin_b", c_float_p)]
 
 
+class AlignerDevWeights(C.Structure):  # parrot_aligner_dev_weights: DEVICE pointers, torch layouts
+    _fields_ = [(n, C.c_void_p * 3) for n in ("conv_w", "bn_weight", "bn_bias", "bn_mean", "bn_var")] + \
+               [(n, C.c_void_p * 2) for n in ("w_ih", "w_hh", "b_ih", "b_hh")] + [("lin_w", C.c_void_p), ("lin_b", C.c_void_p)]
+
+
+class AlignerGrads(C.Structure):  # parrot_aligner_grads: where the backward writes; a null field is not computed
+    _fields_ = [(n, C.c_void_p * 3) for n in ("conv_w", "bn_weight", "bn_bias")] + \
+               [(n, C.c_void_p * 2) for n in ("w_ih", "w_hh", "b_ih", "b_hh")] + [("lin_w", C.c_void_p), ("lin_b", C.c_void_p)]
+
+
 class GanTerm(C.Structure):  # parrot_gan_term_t: 48 bytes
     _fields_ = [("a", C.c_void_p), ("b", C.c_void_p), ("grad_a", C.c_void_p), ("grad_b", C.c_void_p), ("n", C.c_int64),
                 ("op", C.c_int32), ("reserved", C.c_int32)]
@@ -177,6 +187,11 @@ SIGNATURES = {
     "parrot_ctc_loss": (C.c_int, [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, sz, vp]),
     "parrot_ctc_grad_workspace_bytes": (sz, [i32, i32, i32, i32]),
     "parrot_ctc_loss_grad": (C.c_int, [vp, vp, vp, vp, i32, i32, i32, i32, vp, i32, vp, vp, vp, sz, vp]),
+    "parrot_aligner_train_saved_bytes": (sz, [C.POINTER(AlignerCfg), i32, i32]),
+    "parrot_aligner_train_workspace_bytes": (sz, [C.POINTER(AlignerCfg), i32, i32]),
+    "parrot_aligner_train_forward": (C.c_int, [C.POINTER(AlignerCfg), C.POINTER(AlignerDevWeights), vp, i32, i32, i32, vp, vp, vp, sz, vp]),
+    "parrot_aligner_train_backward": (C.c_int, [C.POINTER(AlignerCfg), C.POINTER(AlignerDevWeights), vp, vp, vp, i32, i32,
+                                                C.POINTER(AlignerGrads), vp, sz, vp]),
     "parrot_gan_loss_tile": (i32, []),
     "parrot_gan_loss_workspace_bytes": (sz, [C.POINTER(GanTerm), i32]),
     "parrot_gan_loss": (C.c_int, [C.POINTER(GanTerm), i32, vp, C.c_double, vp, vp, vp, sz, vp]),

@@ -14,6 +14,8 @@ and the CTC loss of utils/aligner/trainer.py:60-71 with its gradient, backed by 
     ctc_loss_trainable(logits, tokens, mel_len, tokens_len) -> loss           the loss as an autograd node (logits only)
     CTCLoss(blank=0, reduction="mean", zero_infinity=False)      torch.nn.CTCLoss's call shape over ctc_loss_trainable
     extract_durations_with_dijkstra(tokens, pred) -> durations   numpy in, numpy out, the reference's signature
+    TrainableAligner(n_mels, num_symbols, lstm_dim, conv_dim)    the same network for TRAINING: batch-statistics forward and the full
+                                                                 backward (aligner_train.py); ``Aligner`` itself is inference only
 
 Padding is NOT masked before the softmax, as in the reference: the backward LSTM of a short row starts inside the padding, so a
 row's logits depend on the length its batch is padded to.  Durations are those of the cheapest monotonic path; among equally cheap
@@ -379,8 +381,8 @@ def ctc_loss_trainable(logits: torch.Tensor, tokens: torch.Tensor, mel_len, toke
                        zero_infinity: bool = False) -> torch.Tensor:
     """``ctc_loss`` as a differentiable function of the logits: same values and dtypes ("mean" 0-dim fp32, "none" (B) fp64, "sum"
     0-dim fp64), and ``.backward()`` runs ``parrot_ctc_loss_grad`` -- deterministic, so it also runs under
-    ``torch.use_deterministic_algorithms(True)``, where torch's own device backward raises.  For a torch-built model: the HIP
-    ``Aligner.forward`` has no backward.  No double backward."""
+    ``torch.use_deterministic_algorithms(True)``, where torch's own device backward raises.  For ``TrainableAligner`` or a torch-built
+    model: the inference ``Aligner.forward`` has no backward.  No double backward."""
     if reduction not in ("mean", "none", "sum"):
         raise ValueError(f"ctc_loss_trainable: reduction must be 'mean', 'none' or 'sum', got {reduction!r}")
     return _CtcLossFn.apply(logits, tokens, mel_len, tokens_len, reduction, zero_infinity)
@@ -422,3 +424,6 @@ def extract_durations_with_dijkstra(tokens: np.ndarray, pred: np.ndarray) -> np.
     t = torch.from_numpy(np.ascontiguousarray(tokens, dtype=np.int64))[None]
     dur, _ = align_durations(p, t, [pred.shape[0]], [tokens.shape[0]])
     return dur[0].cpu().numpy().astype(np.int32)
+
+
+from .aligner_train import TrainableAligner  # noqa: E402,F401  (training: the batch-statistics forward and the full backward)

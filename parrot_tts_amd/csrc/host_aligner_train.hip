@@ -1,0 +1,309 @@
+// host_aligner_train.hip -- training the forced aligner: the batch-statistics forward and the full backward as two stateless calls
+// (kernels and launchers: aligner_train.h / tu_aligner_train.hip).  No handle, no packed weights, no host copy and no
+// synchronisation: every weight is read from the device pointer it is given.
+#include "host_common.h"
+
+#include <algorithm>
+#include <string>
+
+#include "aligner.h"
+#include "aligner_train.h"
+
+using namespace parrot;
+
+namespace {
+
+constexpr long AT_MAX_BT = (long)(65535 / AT_MAX_TAPS) * AT_RCHUNK;  // wgrad_kernel's grid.z = chunks x taps
+
+// What the forward keeps for the backward.  Activations are channel-first (B, C, T) around the convs, (B, T, C) around the LSTM.
+struct TrainSaved {
+    float *r[3], *y[3];        // (B, conv_dim, T): ReLU output (the BatchNorm's input) and BatchNorm output of block i
+    float *mean[3], *invstd[3];  // (conv_dim): the statistics block i normalised with
+    float *gates, *c_all, *h;  // (B, T, 8H) gate activations; (B, T, 2H) cell states; (B, T, 2H) LSTM output
+};
+TrainSaved train_saved(const parrot_aligner_cfg& cfg, Arena& ar, int B, int T) {
+    const size_t BT = (size_t)B * T, H = (size_t)cfg.lstm_dim, D = (size_t)cfg.conv_dim;
+    TrainSaved sv{};
+    for (int i = 0; i < 3; ++i) {
+        sv.r[i] = ar.take<float>(BT * D);
+        sv.y[i] = ar.take<float>(BT * D);
+        sv.mean[i] = ar.take<float>(D);
+        sv.invstd[i] = ar.take<float>(D);
+    }
+    sv.gates = ar.take<float>(BT * 8 * H);
+    sv.c_all = ar.take<float>(BT * 2 * H);
+    sv.h = ar.take<float>(BT * 2 * H);
+    return sv;
+}
+size_t saved_bytes(const parrot_aligner_cfg& cfg, int B, int T) {
+    Arena ar(nullptr, 0);
+    (void)train_saved(cfg, ar, B, T);
+    return align_up(ar.off, 256);
+}
+// One workspace layout for both calls.  The forward uses xproj, hbuf, cbuf and -- when the caller keeps nothing (training = 0,
+// saved = NULL) -- `saved`; the backward uses the rest.
+struct TrainScratch {
+    float *xproj;          // (B, T, 8H)
+    float *hbuf, *cbuf;    // [2][2][B][H], [2][B][H]
+    char* saved;           // saved_bytes
+    float *dlstm, *dgates; // (B, T, 2H), (B, T, 8H)
+    float *dc, *w_hh_t;    // [2][B][H], [2][H][4H]
+    float *da, *db;        // (B, conv_dim, T) each: gradient at a block's output / at its conv's output
+    float* part;           // chunks x the largest weight gradient
+    double* colpart;       // chunks x max(8H, V)
+};
+TrainScratch train_scratch(const parrot_aligner_cfg& cfg, Arena& ar, int B, int T) {
+    const size_t BT = (size_t)B * T, H = (size_t)cfg.lstm_dim, D = (size_t)cfg.conv_dim, V = (size_t)cfg.num_symbols, F = (size_t)cfg.n_mels;
+    const size_t chunks = (size_t)wgrad_chunks((int)BT);
+    TrainScratch w{};
+    w.xproj = ar.take<float>(BT * 8 * H);
+    w.hbuf = ar.take<float>((size_t)2 * 2 * B * H);
+    w.cbuf = ar.take<float>((size_t)2 * B * H);
+    w.saved = ar.take<char>(saved_bytes(cfg, B, T));
+    w.dlstm = ar.take<float>(BT * 2 * H);
+    w.dgates = ar.take<float>(BT * 8 * H);
+    w.dc = ar.take<float>((size_t)2 * B * H);
+    w.w_hh_t = ar.take<float>((size_t)2 * H * 4 * H);
+    w.da = ar.take<float>(BT * D);
+    w.db = ar.take<float>(BT * D);
+    size_t wmax = std::max(std::max(D * D * 5, D * F * 5), std::max(std::max(4 * H * D, 4 * H * H), V * 2 * H));
+    w.part = ar.take<float>(chunks * wmax);
+    w.colpart = ar.take<double>(chunks * std::max(8 * H, V));
+    return w;
+}
+int train_cfg_ok(const parrot_aligner_cfg* cfg, int B, int T, const char* who) {
+    const std::string w(who);
+    if (cfg->n_mels < 1 || cfg->num_symbols < 1 || cfg->lstm_dim < 1 || cfg->conv_dim < 1) return fail(PARROT_E_INVALID, w + ": dimensions must be positive");
+    if (cfg->lstm_dim % 16 || cfg->conv_dim % 16) return fail(PARROT_E_UNSUPPORTED, w + ": conv_dim and lstm_dim must be multiples of 16");
+    if (cfg->lstm_dim > LSTM_MAX_DIM) return fail(PARROT_E_UNSUPPORTED, w + ": lstm_dim > 1024");
+    if (B <= 0 || B > 65535 || T <= 0) return fail(PARROT_E_INVALID, w + ": need 1 <= B <= 65535 and T >= 1");
+    if (T > ALIGN_MAX_T) return fail(PARROT_E_UNSUPPORTED, w + ": T > 32768 frames");
+    if ((long)B * T > AT_MAX_BT) return fail(PARROT_E_UNSUPPORTED, w + ": B T beyond " + std::to_string(AT_MAX_BT) + " frames per batch");
+    return PARROT_OK;
+}
+bool train_cfg_quiet_ok(const parrot_aligner_cfg* cfg, int B, int T) {
+    return cfg && cfg->n_mels >= 1 && cfg->num_symbols >= 1 && cfg->lstm_dim >= 1 && cfg->conv_dim >= 1 && cfg->lstm_dim % 16 == 0 &&
+           cfg->conv_dim % 16 == 0 && cfg->lstm_dim <= LSTM_MAX_DIM && B > 0 && B <= 65535 && T > 0 && T <= ALIGN_MAX_T && (long)B * T <= AT_MAX_BT;
+}
+int weights_ok(const parrot_aligner_dev_weights* w, const char* who) {
+    bool ok = w->lin_w && w->lin_b;
+    for (int i = 0; i < 3; ++i) ok = ok && w->conv_w[i] && w->bn_weight[i] && w->bn_bias[i] && w->bn_mean[i] && w->bn_var[i];
+    for (int d = 0; d < 2; ++d) ok = ok && w->w_ih[d] && w->w_hh[d] && w->b_ih[d] && w->b_hh[d];
+    return ok ? PARROT_OK : fail(PARROT_E_INVALID, std::string(who) + ": null weight");
+}
+
+// one-tap GEMM Y[z] (M x N) = A (M x K) X[z] (K x N): the shape of every 1 x 1 product here
+TapGemmParams gemm1(const float* A, long a_sm, long a_sk, const float* X, long x_sz, long x_sk, long x_sn, float* C, long c_sz, long c_sm, long c_sn,
+                    int M, int N, int K) {
+    TapGemmParams g{};
+    g.ntaps = 1;
+    g.A[0] = A;
+    g.X = X; g.C = C;
+    g.M = M; g.N = N; g.K = K;
+    g.a_sm = a_sm; g.a_sk = a_sk;
+    g.x_sz = x_sz; g.x_sk = x_sk; g.x_sn = x_sn;
+    g.c_sz = c_sz; g.c_sm = c_sm; g.c_sn = c_sn;
+    return g;
+}
+// dA_j = sum_(b, t) dY X^T: partials, then the fp64 sum in chunk order into out[m o_sm + k o_sk + j o_sj]
+int wgrad(WgradParams q, float* part, float* out, long o_sm, long o_sk, long o_sj, hipStream_t s) {
+    q.part = part;
+    HIP_TRY(launch_wgrad(q, s));
+    HIP_TRY(launch_wgrad_reduce(part, wgrad_chunks(q.R), q.ntaps, q.M, q.K, out, o_sm, o_sk, o_sj, s));
+    return PARROT_OK;
+}
+
+}  // namespace
+
+extern "C" size_t parrot_aligner_train_saved_bytes(const parrot_aligner_cfg* cfg, int32_t B, int32_t T) {
+    return train_cfg_quiet_ok(cfg, B, T) ? saved_bytes(*cfg, B, T) : 0;
+}
+extern "C" size_t parrot_aligner_train_workspace_bytes(const parrot_aligner_cfg* cfg, int32_t B, int32_t T) {
+    if (!train_cfg_quiet_ok(cfg, B, T)) return 0;
+    Arena ar(nullptr, 0);
+    (void)train_scratch(*cfg, ar, B, T);
+    return align_up(ar.off, 256);
+}
+
+extern "C" int parrot_aligner_train_forward(const parrot_aligner_cfg* cfg, const parrot_aligner_dev_weights* wt, const float* mel, int32_t B, int32_t T,
+                                            int32_t training, float* logits, void* saved, void* ws, size_t ws_bytes, void* stream) {
+    if (!cfg || !wt || !mel || !logits || !ws) return fail(PARROT_E_INVALID, "aligner_train_forward: null argument");
+    TRY(train_cfg_ok(cfg, B, T, "aligner_train_forward"));
+    TRY(weights_ok(wt, "aligner_train_forward"));
+    if (training && !saved) return fail(PARROT_E_INVALID, "aligner_train_forward: training needs the saved buffer");
+    if (training && (long)B * T == 1) return fail(PARROT_E_INVALID, "aligner_train_forward: Expected more than 1 value per channel when training");
+    hipStream_t s = (hipStream_t)stream;
+    const int H = cfg->lstm_dim, D = cfg->conv_dim, V = cfg->num_symbols, F = cfg->n_mels;
+    Arena ar(ws, ws_bytes);
+    const TrainScratch w = train_scratch(*cfg, ar, B, T);
+    if (!ar.ok) return fail(PARROT_E_NOMEM, "aligner_train_forward: workspace too small");
+    const size_t sv_bytes = saved_bytes(*cfg, B, T);
+    if (poison_word()) {
+        TRY(poison(ws, ws_bytes, s));
+        if (saved) TRY(poison(saved, sv_bytes, s));
+        TRY(poison(logits, (size_t)B * T * V * sizeof(float), s));
+    }
+    Arena sa(saved ? saved : (void*)w.saved, sv_bytes);
+    const TrainSaved sv = train_saved(*cfg, sa, B, T);
+    // 3 x [conv(k = 5, pad 2) -> ReLU -> BatchNorm] on the padded batch as it stands (model.py:16-19, 41-45)
+    for (int i = 0; i < 3; ++i) {
+        const int cin = i ? D : F;
+        TapGemmParams g{};
+        g.ntaps = 5;
+        for (int j = 0; j < 5; ++j) {
+            g.A[j] = wt->conv_w[i] + j;  // (conv_dim, cin, 5)
+            g.shift[j] = j - 2;
+        }
+        g.a_sm = (long)cin * 5; g.a_sk = 5;
+        if (i == 0) { g.X = mel; g.x_sz = (long)T * F; g.x_sk = 1; g.x_sn = F; }  // mel (B, T, n_mels) read transposed
+        else { g.X = sv.y[i - 1]; g.x_sz = (long)D * T; g.x_sk = T; g.x_sn = 1; }
+        g.C = sv.r[i]; g.c_sz = (long)D * T; g.c_sm = T; g.c_sn = 1;
+        g.M = D; g.N = T; g.K = cin;
+        g.relu = 1;
+        HIP_TRY(launch_tap_gemm(g, B, s));
+        BnTrainParams bn{};
+        bn.x = sv.r[i]; bn.y = sv.y[i];
+        bn.gamma = wt->bn_weight[i]; bn.beta = wt->bn_bias[i];
+        bn.run_mean = wt->bn_mean[i]; bn.run_var = wt->bn_var[i];
+        bn.mean = sv.mean[i]; bn.invstd = sv.invstd[i];
+        bn.B = B; bn.C = D; bn.T = T; bn.training = training ? 1 : 0;
+        bn.eps = cfg->bn_eps;
+        HIP_TRY(launch_bn_train(bn, s));
+    }
+    // W_ih x + (b_ih + b_hh) of both directions for all frames, written as (B, T, 8H)
+    for (int d = 0; d < 2; ++d) {
+        TapGemmParams g = gemm1(wt->w_ih[d], D, 1, sv.y[2], (long)D * T, T, 1, w.xproj + (size_t)d * 4 * H, (long)T * 8 * H, 1, 8 * H, 4 * H, T, D);
+        g.bias0 = wt->b_ih[d];
+        g.bias1 = wt->b_hh[d];
+        HIP_TRY(launch_tap_gemm(g, B, s));
+    }
+    const size_t hn = (size_t)2 * B * H;
+    HIP_TRY(hipMemsetAsync(w.hbuf, 0, hn * sizeof(float), s));  // h_0 = c_0 = 0
+    HIP_TRY(hipMemsetAsync(w.cbuf, 0, hn * sizeof(float), s));
+    LstmTrainParams q{};
+    q.w_hh[0] = wt->w_hh[0]; q.w_hh[1] = wt->w_hh[1];
+    q.xproj = w.xproj; q.c = w.cbuf; q.out = sv.h; q.gates = sv.gates; q.c_all = sv.c_all;
+    q.B = B; q.T = T; q.H = H;
+    for (int step = 0; step < T; ++step) {
+        q.step = step;
+        q.h_prev = w.hbuf + (size_t)(step & 1) * hn;
+        q.h_next = w.hbuf + (size_t)((step + 1) & 1) * hn;
+        HIP_TRY(launch_lstm_train_step(q, s));
+    }
+    TapGemmParams g = gemm1(wt->lin_w, 2 * H, 1, sv.h, (long)T * 2 * H, 1, 2 * H, logits, (long)T * V, 1, V, V, T, 2 * H);
+    g.bias0 = wt->lin_b;
+    HIP_TRY(launch_tap_gemm(g, B, s));
+    return PARROT_OK;
+}
+
+extern "C" int parrot_aligner_train_backward(const parrot_aligner_cfg* cfg, const parrot_aligner_dev_weights* wt, const float* mel, const void* saved,
+                                             const float* grad_logits, int32_t B, int32_t T, const parrot_aligner_grads* gr, void* ws, size_t ws_bytes,
+                                             void* stream) {
+    if (!cfg || !wt || !mel || !saved || !grad_logits || !gr || !ws) return fail(PARROT_E_INVALID, "aligner_train_backward: null argument");
+    TRY(train_cfg_ok(cfg, B, T, "aligner_train_backward"));
+    TRY(weights_ok(wt, "aligner_train_backward"));
+    if ((long)B * T == 1) return fail(PARROT_E_INVALID, "aligner_train_backward: Expected more than 1 value per channel when training");
+    hipStream_t s = (hipStream_t)stream;
+    const int H = cfg->lstm_dim, D = cfg->conv_dim, V = cfg->num_symbols, F = cfg->n_mels, BT = B * T;
+    Arena ar(ws, ws_bytes);
+    const TrainScratch w = train_scratch(*cfg, ar, B, T);
+    if (!ar.ok) return fail(PARROT_E_NOMEM, "aligner_train_backward: workspace too small");
+    if (poison_word()) {
+        TRY(poison(ws, ws_bytes, s));
+        for (int i = 0; i < 3; ++i) {
+            TRY(poison(gr->conv_w[i], (size_t)D * (i ? D : F) * 5 * sizeof(float), s));
+            TRY(poison(gr->bn_weight[i], (size_t)D * sizeof(float), s));
+            TRY(poison(gr->bn_bias[i], (size_t)D * sizeof(float), s));
+        }
+        for (int d = 0; d < 2; ++d) {
+            TRY(poison(gr->w_ih[d], (size_t)4 * H * D * sizeof(float), s));
+            TRY(poison(gr->w_hh[d], (size_t)4 * H * H * sizeof(float), s));
+            TRY(poison(gr->b_ih[d], (size_t)4 * H * sizeof(float), s));
+            TRY(poison(gr->b_hh[d], (size_t)4 * H * sizeof(float), s));
+        }
+        TRY(poison(gr->lin_w, (size_t)V * 2 * H * sizeof(float), s));
+        TRY(poison(gr->lin_b, (size_t)V * sizeof(float), s));
+    }
+    Arena sa(const_cast<void*>(saved), saved_bytes(*cfg, B, T));
+    const TrainSaved sv = train_saved(*cfg, sa, B, T);
+    const long T2 = (long)T * 2 * H, T8 = (long)T * 8 * H, DT = (long)D * T;
+
+    // ---- Linear(2H -> V): db, dW, dX -------------------------------------------------------------
+    if (gr->lin_b) HIP_TRY(launch_colsum(grad_logits, BT, V, V, w.colpart, gr->lin_b, nullptr, s));
+    if (gr->lin_w) {
+        WgradParams q{};
+        q.dY = grad_logits; q.y_sz = (long)T * V; q.y_sm = 1; q.y_st = V;
+        q.X = sv.h; q.x_sz = T2; q.x_sk = 1; q.x_st = 2 * H;
+        q.M = V; q.K = 2 * H; q.T = T; q.R = BT; q.ntaps = 1;
+        TRY(wgrad(q, w.part, gr->lin_w, 2 * H, 1, 0, s));
+    }
+    // dlstm (B, T, 2H) = grad_logits lin_w: A = lin_w^T through its strides
+    HIP_TRY(launch_tap_gemm(gemm1(wt->lin_w, 1, 2 * H, grad_logits, (long)T * V, 1, V, w.dlstm, T2, 1, 2 * H, 2 * H, T, V), B, s));
+
+    // ---- the LSTM back through time, both directions per launch ----------------------------------
+    for (int d = 0; d < 2; ++d) HIP_TRY(launch_align_transpose(wt->w_hh[d], w.w_hh_t + (size_t)d * H * 4 * H, 1, 4 * H, H, s));
+    HIP_TRY(hipMemsetAsync(w.dc, 0, (size_t)2 * B * H * sizeof(float), s));
+    LstmBwdParams lb{};
+    lb.w_hh_t = w.w_hh_t; lb.gates = sv.gates; lb.c_all = sv.c_all; lb.dout = w.dlstm; lb.dgates = w.dgates; lb.dc = w.dc;
+    lb.B = B; lb.T = T; lb.H = H;
+    for (int step = 0; step < T; ++step) {
+        lb.step = step;
+        HIP_TRY(launch_lstm_bwd_step(lb, s));
+    }
+    for (int d = 0; d < 2; ++d) {
+        const float* dg = w.dgates + (size_t)d * 4 * H;
+        if (gr->b_ih[d] || gr->b_hh[d])  // db_ih = db_hh = sum dgates: one sum, written twice
+            HIP_TRY(launch_colsum(dg, BT, 4 * H, 8 * H, w.colpart, gr->b_ih[d] ? gr->b_ih[d] : gr->b_hh[d], gr->b_ih[d] ? gr->b_hh[d] : nullptr, s));
+        WgradParams q{};
+        q.dY = dg; q.y_sz = T8; q.y_sm = 1; q.y_st = 8 * H;
+        q.M = 4 * H; q.T = T; q.R = BT; q.ntaps = 1;
+        if (gr->w_ih[d]) {
+            q.X = sv.y[2]; q.x_sz = DT; q.x_sk = T; q.x_st = 1; q.K = D;
+            TRY(wgrad(q, w.part, gr->w_ih[d], D, 1, 0, s));
+        }
+        if (gr->w_hh[d]) {  // dW_hh = sum_t dgates_t^T h at the step before t: t - 1 forward, t + 1 backward; the zero fill is h_0 = 0
+            q.X = sv.h + (size_t)d * H; q.x_sz = T2; q.x_sk = 1; q.x_st = 2 * H; q.K = H;
+            q.shift[0] = d ? 1 : -1;
+            TRY(wgrad(q, w.part, gr->w_hh[d], H, 1, 0, s));
+        }
+    }
+    {   // dy_2 (B, conv_dim, T) = W_ih^T dgates + W_ih_reverse^T dgates_reverse: two taps without a shift
+        TapGemmParams g = gemm1(wt->w_ih[0], 1, D, w.dgates, T8, 1, 8 * H, w.da, DT, T, 1, D, T, 4 * H);
+        g.ntaps = 2;
+        g.A[1] = wt->w_ih[1];
+        g.x_off[1] = 4 * H;
+        HIP_TRY(launch_tap_gemm(g, B, s));
+    }
+    // ---- the conv blocks, last to first: BatchNorm + ReLU backward, conv weight gradient, conv data gradient -----
+    for (int i = 2; i >= 0; --i) {
+        const int cin = i ? D : F;
+        BnBwdParams bb{};
+        bb.dy = w.da; bb.x = sv.r[i]; bb.dx = w.db;
+        bb.gamma = wt->bn_weight[i]; bb.mean = sv.mean[i]; bb.invstd = sv.invstd[i];
+        bb.dgamma = gr->bn_weight[i]; bb.dbeta = gr->bn_bias[i];
+        bb.B = B; bb.C = D; bb.T = T;
+        HIP_TRY(launch_bn_relu_bwd(bb, s));
+        if (gr->conv_w[i]) {
+            WgradParams q{};
+            q.dY = w.db; q.y_sz = DT; q.y_sm = T; q.y_st = 1;
+            if (i == 0) { q.X = mel; q.x_sz = (long)T * F; q.x_sk = 1; q.x_st = F; }
+            else { q.X = sv.y[i - 1]; q.x_sz = DT; q.x_sk = T; q.x_st = 1; }
+            q.M = D; q.K = cin; q.T = T; q.R = BT; q.ntaps = 5;
+            for (int j = 0; j < 5; ++j) q.shift[j] = j - 2;
+            TRY(wgrad(q, w.part, gr->conv_w[i], (long)cin * 5, 5, 1, s));
+        }
+        if (i == 0) break;  // mel gets no gradient
+        TapGemmParams g{};  // dy_{i-1}[k][t] = sum_j sum_m w[m][k][j] dconv[m][t - (j - 2)]
+        g.ntaps = 5;
+        for (int j = 0; j < 5; ++j) {
+            g.A[j] = wt->conv_w[i] + j;
+            g.shift[j] = 2 - j;
+        }
+        g.a_sm = 5; g.a_sk = (long)D * 5;
+        g.X = w.db; g.x_sz = DT; g.x_sk = T; g.x_sn = 1;
+        g.C = w.da; g.c_sz = DT; g.c_sm = T; g.c_sn = 1;
+        g.M = D; g.N = T; g.K = D;
+        HIP_TRY(launch_tap_gemm(g, B, s));
+    }
+    return PARROT_OK;
+}
