@@ -92,6 +92,65 @@ int parrot_debug_argmax_guard(const float* logits, int32_t B, int32_t V, int32_t
 /* Stage taps of the aligner: while set, every parrot_aligner_forward copies the activation after the third BatchNorm, channel-first
  * (B, conv_dim, T), to bn3_dev and the LSTM output (B, T, 2 lstm_dim) to lstm_dev (DEVICE buffers; NULL entries are skipped). */
 int parrot_aligner_debug_stages(parrot_aligner_t*, float* bn3_dev, float* lstm_dev);
+/* Tests: the aligner's training kernels (csrc/aligner_train.h) on their own, through the launch code of parrot_aligner_train_forward /
+ * _backward (csrc/host_aligner_train.hip), on caller-owned DEVICE buffers.  Each descriptor mirrors the kernel's parameter struct;
+ * every buffer it names is a parrot_debug_buf: the pointer and the number of floats behind it.  Before any launch the entry point
+ * computes on the host the smallest and largest element index the strides, offsets, shifts and sizes can reach in every buffer:
+ * a null or empty argument, a size < 1, a reach below 0 or at / beyond the count, or a workspace that is too small:
+ * PARROT_E_INVALID; more than PARROT_DEBUG_MAX_TAPS taps, or a grid beyond what the launchers take: PARROT_E_UNSUPPORTED.
+ * parrot_debug_tap_gemm: C[z][m][n] = act(sum_j sum_k A_j[m][k] X[z][k][n + shift_j] + bias0[m] + bias1[m]), z < Z; X is zero outside
+ *   0 <= n + shift_j < N; element (m, k) of tap j at A[j].p + m a_sm + k a_sk, X[z][k][n] at X.p + x_off[j] + z x_sz + k x_sk + n x_sn,
+ *   C[z][m][n] at C.p + z c_sz + m c_sm + n c_sn; bias0 nullable, bias1 only beside bias0.  Elements of C the strides do not address
+ *   are not written.
+ * parrot_debug_wgrad: out[m o_sm + k o_sk + j o_sj] = sum over b < R / T, t < T of dY[b][m][t] X[b][k][t + shift_j] (X zero outside
+ *   0 <= t + shift_j < T; R a multiple of T): fp32 partials per 256 (b, t) pairs, added in fp64 and rounded once.  ws:
+ *   parrot_debug_wgrad_workspace_bytes(R, ntaps, M, K) (0 for sizes that are not valid).
+ * parrot_debug_colsum: out0[m] (and out1[m], nullable) = sum_r src[r ld + m], r < R, m < M, in fp64, rounded once.  ws:
+ *   parrot_debug_colsum_workspace_bytes(R, M).
+ * parrot_debug_bn_train / parrot_debug_bn_relu_bwd: BatchNorm1d over (B, C, T) on batch statistics (training; B T >= 2) or the
+ *   running ones, and its backward fused with the ReLU's (x is the ReLU's output; dx may be dy; dgamma / dbeta nullable). */
+#define PARROT_DEBUG_MAX_TAPS 5
+typedef struct parrot_debug_buf {
+    float* p;
+    int64_t n;
+} parrot_debug_buf;
+typedef struct parrot_debug_tap_gemm_desc {
+    parrot_debug_buf A[PARROT_DEBUG_MAX_TAPS];
+    int64_t x_off[PARROT_DEBUG_MAX_TAPS];
+    int32_t shift[PARROT_DEBUG_MAX_TAPS];
+    int32_t ntaps;
+    parrot_debug_buf X, C, bias0, bias1;
+    int32_t M, N, K, Z;
+    int64_t a_sm, a_sk, x_sz, x_sk, x_sn, c_sz, c_sm, c_sn;
+    int32_t relu;
+} parrot_debug_tap_gemm_desc;
+typedef struct parrot_debug_wgrad_desc {
+    parrot_debug_buf dY, X, out;
+    int32_t M, K, T, R, ntaps;
+    int32_t shift[PARROT_DEBUG_MAX_TAPS];
+    int64_t y_sz, y_sm, y_st, x_sz, x_sk, x_st, o_sm, o_sk, o_sj;
+} parrot_debug_wgrad_desc;
+typedef struct parrot_debug_colsum_desc {
+    parrot_debug_buf src, out0, out1;
+    int32_t R, M;
+    int64_t ld;
+} parrot_debug_colsum_desc;
+typedef struct parrot_debug_bn_train_desc {
+    parrot_debug_buf x, y, gamma, beta, run_mean, run_var, mean, invstd;
+    int32_t B, C, T, training;
+    float eps;
+} parrot_debug_bn_train_desc;
+typedef struct parrot_debug_bn_bwd_desc {
+    parrot_debug_buf dy, x, dx, gamma, mean, invstd, dgamma, dbeta;
+    int32_t B, C, T;
+} parrot_debug_bn_bwd_desc;
+int parrot_debug_tap_gemm(const parrot_debug_tap_gemm_desc* d, void* stream);
+size_t parrot_debug_wgrad_workspace_bytes(int32_t R, int32_t ntaps, int32_t M, int32_t K);
+int parrot_debug_wgrad(const parrot_debug_wgrad_desc* d, void* ws, size_t ws_bytes, void* stream);
+size_t parrot_debug_colsum_workspace_bytes(int32_t R, int32_t M);
+int parrot_debug_colsum(const parrot_debug_colsum_desc* d, void* ws, size_t ws_bytes, void* stream);
+int parrot_debug_bn_train(const parrot_debug_bn_train_desc* d, void* stream);
+int parrot_debug_bn_relu_bwd(const parrot_debug_bn_bwd_desc* d, void* stream);
 
 #ifdef __cplusplus
 }

@@ -90,6 +90,40 @@ class GanTerm(C.Structure):  # parrot_gan_term_t: 48 bytes
                 ("op", C.c_int32), ("reserved", C.c_int32)]
 
 
+DEBUG_MAX_TAPS = 5  # PARROT_DEBUG_MAX_TAPS of include/parrot_hip_debug.h
+
+
+class DebugBuf(C.Structure):  # parrot_debug_buf: a DEVICE buffer and the number of floats behind the pointer
+    _fields_ = [("p", C.c_void_p), ("n", C.c_int64)]
+
+
+class DebugTapGemmDesc(C.Structure):
+    _fields_ = [("A", DebugBuf * DEBUG_MAX_TAPS), ("x_off", C.c_int64 * DEBUG_MAX_TAPS), ("shift", C.c_int32 * DEBUG_MAX_TAPS),
+                ("ntaps", C.c_int32)] + [(n, DebugBuf) for n in ("X", "C", "bias0", "bias1")] + \
+               [(n, C.c_int32) for n in ("M", "N", "K", "Z")] + \
+               [(n, C.c_int64) for n in ("a_sm", "a_sk", "x_sz", "x_sk", "x_sn", "c_sz", "c_sm", "c_sn")] + [("relu", C.c_int32)]
+
+
+class DebugWgradDesc(C.Structure):
+    _fields_ = [(n, DebugBuf) for n in ("dY", "X", "out")] + [(n, C.c_int32) for n in ("M", "K", "T", "R", "ntaps")] + \
+               [("shift", C.c_int32 * DEBUG_MAX_TAPS)] + \
+               [(n, C.c_int64) for n in ("y_sz", "y_sm", "y_st", "x_sz", "x_sk", "x_st", "o_sm", "o_sk", "o_sj")]
+
+
+class DebugColsumDesc(C.Structure):
+    _fields_ = [(n, DebugBuf) for n in ("src", "out0", "out1")] + [("R", C.c_int32), ("M", C.c_int32), ("ld", C.c_int64)]
+
+
+class DebugBnTrainDesc(C.Structure):
+    _fields_ = [(n, DebugBuf) for n in ("x", "y", "gamma", "beta", "run_mean", "run_var", "mean", "invstd")] + \
+               [(n, C.c_int32) for n in ("B", "C", "T", "training")] + [("eps", C.c_float)]
+
+
+class DebugBnBwdDesc(C.Structure):
+    _fields_ = [(n, DebugBuf) for n in ("dy", "x", "dx", "gamma", "mean", "invstd", "dgamma", "dbeta")] + \
+               [(n, C.c_int32) for n in ("B", "C", "T")]
+
+
 GAN_L1, GAN_SQ1, GAN_SQ0 = 0, 1, 2  # PARROT_GAN_* of include/parrot_hip.h
 GAN_MAX_TERMS, GAN_GRID_CAP = 64, 2048  # PARROT_GAN_MAX_TERMS, PARROT_GAN_GRID_CAP
 
@@ -192,6 +226,13 @@ SIGNATURES = {
     "parrot_aligner_train_forward": (C.c_int, [C.POINTER(AlignerCfg), C.POINTER(AlignerDevWeights), vp, i32, i32, i32, vp, vp, vp, sz, vp]),
     "parrot_aligner_train_backward": (C.c_int, [C.POINTER(AlignerCfg), C.POINTER(AlignerDevWeights), vp, vp, vp, i32, i32,
                                                 C.POINTER(AlignerGrads), vp, sz, vp]),
+    "parrot_debug_tap_gemm": (C.c_int, [C.POINTER(DebugTapGemmDesc), vp]),
+    "parrot_debug_wgrad_workspace_bytes": (sz, [i32, i32, i32, i32]),
+    "parrot_debug_wgrad": (C.c_int, [C.POINTER(DebugWgradDesc), vp, sz, vp]),
+    "parrot_debug_colsum_workspace_bytes": (sz, [i32, i32]),
+    "parrot_debug_colsum": (C.c_int, [C.POINTER(DebugColsumDesc), vp, sz, vp]),
+    "parrot_debug_bn_train": (C.c_int, [C.POINTER(DebugBnTrainDesc), vp]),
+    "parrot_debug_bn_relu_bwd": (C.c_int, [C.POINTER(DebugBnBwdDesc), vp]),
     "parrot_gan_loss_tile": (i32, []),
     "parrot_gan_loss_workspace_bytes": (sz, [C.POINTER(GanTerm), i32]),
     "parrot_gan_loss": (C.c_int, [C.POINTER(GanTerm), i32, vp, C.c_double, vp, vp, vp, sz, vp]),

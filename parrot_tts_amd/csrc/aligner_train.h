@@ -370,7 +370,14 @@ __global__ __launch_bounds__(256) void bn_relu_bwd_kernel(const BnBwdParams p) {
         const int b = i / T, t = i - b * T;
         const float xv = x[b * bs + t];
         const float xh = __fmul_rn(__fsub_rn(xv, mean), invstd);
-        const float v = __fmul_rn(k, __fsub_rn(__fsub_rn(dy[b * bs + t], m1), __fmul_rn(xh, m2)));
+        float v;
+        {
+            // (HIP's __fmul_rn / __fsub_rn are a plain `*` and `-` compiled under the default -ffp-contract=fast, so nested as
+            // a - xh m2 they fuse into one FMA and dx is not the chain of single roundings documented above: plain operators
+            // under the pragma stay apart)
+#pragma clang fp contract(off)
+            v = k * ((dy[b * bs + t] - m1) - xh * m2);
+        }
         dx[b * bs + t] = xv > 0.f ? v : 0.f;
     }
 }

@@ -307,3 +307,161 @@ extern "C" int parrot_aligner_train_backward(const parrot_aligner_cfg* cfg, cons
     }
     return PARROT_OK;
 }
+
+// ---------------------------------------------------------------------------------------------
+// Debug entry points (include/parrot_hip_debug.h): the kernels above on caller-owned buffers, through gemm1 / wgrad() / the
+// launch_* helpers.  Nothing is launched before every index the descriptor can reach has been bounded on the host.
+// ---------------------------------------------------------------------------------------------
+namespace {
+
+static_assert(PARROT_DEBUG_MAX_TAPS == AT_MAX_TAPS, "the debug descriptors hold one slot per tap");
+
+// smallest and largest element index of sum_i idx_i stride_i + offset, idx_i in [lo_i, hi_i]
+struct Reach {
+    __int128 lo = 0, hi = 0;
+    Reach& off(long o) { lo += o; hi += o; return *this; }
+    Reach& dim(long first, long last, long stride) {
+        const __int128 a = (__int128)first * stride, b = (__int128)last * stride;
+        lo += a < b ? a : b;
+        hi += a < b ? b : a;
+        return *this;
+    }
+    Reach& dim(long n, long stride) { return dim(0, n - 1, stride); }
+};
+int reach_ok(const Reach& r, const parrot_debug_buf& b, const std::string& who, const char* name) {
+    if (!b.p || b.n < 1) return fail(PARROT_E_INVALID, who + ": " + name + " is null or empty");
+    if (r.lo < 0) return fail(PARROT_E_INVALID, who + ": the strides reach below element 0 of " + name);
+    if (r.hi >= b.n) return fail(PARROT_E_INVALID, who + ": the strides reach beyond the " + std::to_string(b.n) + " elements of " + name);
+    return PARROT_OK;
+}
+// what a launcher refused before launching anything is a limit of the kernels, not a fault of the device
+int launched(hipError_t e, const std::string& who) {
+    if (e == hipErrorInvalidValue) return fail(PARROT_E_UNSUPPORTED, who + ": beyond the launcher's limits (taps, grid size)");
+    if (e != hipSuccess) return fail(PARROT_E_HIP, who + ": " + hipGetErrorString(e));
+    return PARROT_OK;
+}
+bool wgrad_sizes_ok(long R, long ntaps, long M, long K) { return R >= 1 && ntaps >= 1 && ntaps <= AT_MAX_TAPS && M >= 1 && K >= 1; }
+
+}  // namespace
+
+extern "C" int parrot_debug_tap_gemm(const parrot_debug_tap_gemm_desc* d, void* stream) {
+    const std::string who = "debug_tap_gemm";
+    if (!d) return fail(PARROT_E_INVALID, who + ": null argument");
+    if (d->ntaps < 1 || d->M < 1 || d->N < 1 || d->K < 1 || d->Z < 1) return fail(PARROT_E_INVALID, who + ": ntaps, M, N, K and Z must be positive");
+    if (d->ntaps > AT_MAX_TAPS) return fail(PARROT_E_UNSUPPORTED, who + ": more than 5 taps");
+    if (d->bias1.p && !d->bias0.p) return fail(PARROT_E_INVALID, who + ": bias1 without bias0");
+    for (int j = 0; j < d->ntaps; ++j) {
+        TRY(reach_ok(Reach().dim(d->M, d->a_sm).dim(d->K, d->a_sk), d->A[j], who, "A"));
+        const long lo = std::max<long>(0, d->shift[j]), hi = std::min<long>(d->N - 1, (long)d->N - 1 + d->shift[j]);  // the columns of X tap j reads
+        if (!d->X.p || d->X.n < 1) return fail(PARROT_E_INVALID, who + ": X is null or empty");
+        if (lo <= hi) TRY(reach_ok(Reach().off(d->x_off[j]).dim(d->Z, d->x_sz).dim(d->K, d->x_sk).dim(lo, hi, d->x_sn), d->X, who, "X"));
+    }
+    TRY(reach_ok(Reach().dim(d->Z, d->c_sz).dim(d->M, d->c_sm).dim(d->N, d->c_sn), d->C, who, "C"));
+    if (d->bias0.p) TRY(reach_ok(Reach().dim(d->M, 1), d->bias0, who, "bias0"));
+    if (d->bias1.p) TRY(reach_ok(Reach().dim(d->M, 1), d->bias1, who, "bias1"));
+    TapGemmParams g = gemm1(d->A[0].p, d->a_sm, d->a_sk, d->X.p, d->x_sz, d->x_sk, d->x_sn, d->C.p, d->c_sz, d->c_sm, d->c_sn, d->M, d->N, d->K);
+    g.ntaps = d->ntaps;
+    for (int j = 0; j < d->ntaps; ++j) {
+        g.A[j] = d->A[j].p;
+        g.x_off[j] = d->x_off[j];
+        g.shift[j] = d->shift[j];
+    }
+    g.bias0 = d->bias0.p;
+    g.bias1 = d->bias1.p;
+    g.relu = d->relu ? 1 : 0;
+    return launched(launch_tap_gemm(g, d->Z, (hipStream_t)stream), who);
+}
+
+extern "C" size_t parrot_debug_wgrad_workspace_bytes(int32_t R, int32_t ntaps, int32_t M, int32_t K) {
+    return wgrad_sizes_ok(R, ntaps, M, K) ? (size_t)wgrad_chunks(R) * ntaps * M * K * sizeof(float) : 0;
+}
+extern "C" int parrot_debug_wgrad(const parrot_debug_wgrad_desc* d, void* ws, size_t ws_bytes, void* stream) {
+    const std::string who = "debug_wgrad";
+    if (!d || !ws) return fail(PARROT_E_INVALID, who + ": null argument");
+    if (d->ntaps < 1 || d->M < 1 || d->K < 1 || d->T < 1 || d->R < 1) return fail(PARROT_E_INVALID, who + ": ntaps, M, K, T and R must be positive");
+    if (d->ntaps > AT_MAX_TAPS) return fail(PARROT_E_UNSUPPORTED, who + ": more than 5 taps");
+    if (d->R % d->T) return fail(PARROT_E_INVALID, who + ": R must be a multiple of T");
+    const int B = d->R / d->T;
+    TRY(reach_ok(Reach().dim(B, d->y_sz).dim(d->M, d->y_sm).dim(d->T, d->y_st), d->dY, who, "dY"));
+    if (!d->X.p || d->X.n < 1) return fail(PARROT_E_INVALID, who + ": X is null or empty");
+    for (int j = 0; j < d->ntaps; ++j) {
+        const long lo = std::max<long>(0, d->shift[j]), hi = std::min<long>(d->T - 1, (long)d->T - 1 + d->shift[j]);  // the frames of X tap j reads
+        if (lo <= hi) TRY(reach_ok(Reach().dim(B, d->x_sz).dim(d->K, d->x_sk).dim(lo, hi, d->x_st), d->X, who, "X"));
+    }
+    TRY(reach_ok(Reach().dim(d->M, d->o_sm).dim(d->K, d->o_sk).dim(d->ntaps, d->o_sj), d->out, who, "out"));
+    if (ws_bytes < parrot_debug_wgrad_workspace_bytes(d->R, d->ntaps, d->M, d->K)) return fail(PARROT_E_INVALID, who + ": workspace too small");
+    if ((long)wgrad_chunks(d->R) * d->ntaps > 65535 || (d->M + 63) / 64 > 65535)  // (launch_wgrad's own limits, before the workspace is touched)
+        return fail(PARROT_E_UNSUPPORTED, who + ": beyond the launcher's limits (taps, grid size)");
+    hipStream_t s = (hipStream_t)stream;
+    if (poison_word()) TRY(poison(ws, parrot_debug_wgrad_workspace_bytes(d->R, d->ntaps, d->M, d->K), s));
+    WgradParams q{};
+    q.dY = d->dY.p; q.y_sz = d->y_sz; q.y_sm = d->y_sm; q.y_st = d->y_st;
+    q.X = d->X.p; q.x_sz = d->x_sz; q.x_sk = d->x_sk; q.x_st = d->x_st;
+    q.M = d->M; q.K = d->K; q.T = d->T; q.R = d->R; q.ntaps = d->ntaps;
+    for (int j = 0; j < d->ntaps; ++j) q.shift[j] = d->shift[j];
+    return wgrad(q, (float*)ws, d->out.p, d->o_sm, d->o_sk, d->o_sj, s);
+}
+
+extern "C" size_t parrot_debug_colsum_workspace_bytes(int32_t R, int32_t M) {
+    return R >= 1 && M >= 1 ? (size_t)wgrad_chunks(R) * M * sizeof(double) : 0;
+}
+extern "C" int parrot_debug_colsum(const parrot_debug_colsum_desc* d, void* ws, size_t ws_bytes, void* stream) {
+    const std::string who = "debug_colsum";
+    if (!d || !ws) return fail(PARROT_E_INVALID, who + ": null argument");
+    if (d->R < 1 || d->M < 1) return fail(PARROT_E_INVALID, who + ": R and M must be positive");
+    TRY(reach_ok(Reach().dim(d->R, d->ld).dim(d->M, 1), d->src, who, "src"));
+    TRY(reach_ok(Reach().dim(d->M, 1), d->out0, who, "out0"));
+    if (d->out1.p) TRY(reach_ok(Reach().dim(d->M, 1), d->out1, who, "out1"));
+    const size_t need = parrot_debug_colsum_workspace_bytes(d->R, d->M);
+    if (ws_bytes < need) return fail(PARROT_E_INVALID, who + ": workspace too small");
+    if (wgrad_chunks(d->R) > 65535)  // (launch_colsum's own limit, before the workspace is touched)
+        return fail(PARROT_E_UNSUPPORTED, who + ": beyond the launcher's limits (grid size)");
+    hipStream_t s = (hipStream_t)stream;
+    if (poison_word()) TRY(poison(ws, need, s));
+    return launched(launch_colsum(d->src.p, d->R, d->M, d->ld, (double*)ws, d->out0.p, d->out1.p, s), who);
+}
+
+extern "C" int parrot_debug_bn_train(const parrot_debug_bn_train_desc* d, void* stream) {
+    const std::string who = "debug_bn_train";
+    if (!d) return fail(PARROT_E_INVALID, who + ": null argument");
+    if (d->B < 1 || d->C < 1 || d->T < 1) return fail(PARROT_E_INVALID, who + ": B, C and T must be positive");
+    if (d->training && (long)d->B * d->T < 2) return fail(PARROT_E_INVALID, who + ": Expected more than 1 value per channel when training");
+    const Reach all = Reach().dim(d->B, (long)d->C * d->T).dim(d->C, d->T).dim(d->T, 1), chan = Reach().dim(d->C, 1);
+    TRY(reach_ok(all, d->x, who, "x"));
+    TRY(reach_ok(all, d->y, who, "y"));
+    TRY(reach_ok(chan, d->gamma, who, "gamma"));
+    TRY(reach_ok(chan, d->beta, who, "beta"));
+    TRY(reach_ok(chan, d->run_mean, who, "run_mean"));
+    TRY(reach_ok(chan, d->run_var, who, "run_var"));
+    TRY(reach_ok(chan, d->mean, who, "mean"));
+    TRY(reach_ok(chan, d->invstd, who, "invstd"));
+    BnTrainParams bn{};
+    bn.x = d->x.p; bn.y = d->y.p;
+    bn.gamma = d->gamma.p; bn.beta = d->beta.p;
+    bn.run_mean = d->run_mean.p; bn.run_var = d->run_var.p;
+    bn.mean = d->mean.p; bn.invstd = d->invstd.p;
+    bn.B = d->B; bn.C = d->C; bn.T = d->T; bn.training = d->training ? 1 : 0;
+    bn.eps = d->eps;
+    return launched(launch_bn_train(bn, (hipStream_t)stream), who);
+}
+
+extern "C" int parrot_debug_bn_relu_bwd(const parrot_debug_bn_bwd_desc* d, void* stream) {
+    const std::string who = "debug_bn_relu_bwd";
+    if (!d) return fail(PARROT_E_INVALID, who + ": null argument");
+    if (d->B < 1 || d->C < 1 || d->T < 1) return fail(PARROT_E_INVALID, who + ": B, C and T must be positive");
+    const Reach all = Reach().dim(d->B, (long)d->C * d->T).dim(d->C, d->T).dim(d->T, 1), chan = Reach().dim(d->C, 1);
+    TRY(reach_ok(all, d->dy, who, "dy"));
+    TRY(reach_ok(all, d->x, who, "x"));
+    TRY(reach_ok(all, d->dx, who, "dx"));
+    TRY(reach_ok(chan, d->gamma, who, "gamma"));
+    TRY(reach_ok(chan, d->mean, who, "mean"));
+    TRY(reach_ok(chan, d->invstd, who, "invstd"));
+    if (d->dgamma.p) TRY(reach_ok(chan, d->dgamma, who, "dgamma"));
+    if (d->dbeta.p) TRY(reach_ok(chan, d->dbeta, who, "dbeta"));
+    BnBwdParams bb{};
+    bb.dy = d->dy.p; bb.x = d->x.p; bb.dx = d->dx.p;
+    bb.gamma = d->gamma.p; bb.mean = d->mean.p; bb.invstd = d->invstd.p;
+    bb.dgamma = d->dgamma.p; bb.dbeta = d->dbeta.p;
+    bb.B = d->B; bb.C = d->C; bb.T = d->T;
+    return launched(launch_bn_relu_bwd(bb, (hipStream_t)stream), who);
+}

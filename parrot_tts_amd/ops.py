@@ -297,3 +297,87 @@ def debug_argmax_guard(logits: torch.Tensor, guard: float, row0: int = 0, refine
                                                         start, dptr(out["ids"]), dptr(out["glist"]), dptr(out["gstat"]), dptr(out["gref"]),
                                                         dptr(out["status"]), stream_ptr(dev)))
     return out
+
+
+# ---- the aligner's training kernels on their own (tests; include/parrot_hip_debug.h) --------------------------------------------------------
+# A set ``p`` is a dict with the names of the kernel's parameter struct (tests/aligner_train_kernels_ref.py writes the model's own);
+# ``x_base`` / ``c_base`` / ``y_base`` / per-tap ``a_off`` are element offsets into the flat buffers.  The *_desc functions only fill
+# a descriptor and take any parrot_debug_buf (the refusal tests hand in made-up ones and call the library without a device).
+def debug_buf(t: Optional[torch.Tensor], base: int = 0) -> _lib.DebugBuf:
+    """A flat fp32 device tensor from element ``base`` on; None: the null buffer."""
+    if t is None:
+        return _lib.DebugBuf(None, 0)
+    require_cuda(t, "buffer")
+    assert t.dtype == torch.float32 and t.is_contiguous() and 0 <= base < t.numel()
+    return _lib.DebugBuf(t.data_ptr() + 4 * base, t.numel() - base)
+
+
+def _offset_buf(b: _lib.DebugBuf, base: int) -> _lib.DebugBuf:
+    return _lib.DebugBuf((b.p or 0) + 4 * base if b.p else None, b.n - base)
+
+
+def tap_gemm_desc(p: dict, A: _lib.DebugBuf, X: _lib.DebugBuf, Cb: _lib.DebugBuf, bias0=None, bias1=None) -> _lib.DebugTapGemmDesc:
+    d = _lib.DebugTapGemmDesc()
+    d.ntaps = p["ntaps"]
+    for j in range(min(p["ntaps"], _lib.DEBUG_MAX_TAPS)):
+        d.A[j] = _offset_buf(A, p["a_off"][j])
+        d.x_off[j], d.shift[j] = p["x_off"][j], p["shift"][j]
+    d.X, d.C = _offset_buf(X, p.get("x_base", 0)), _offset_buf(Cb, p.get("c_base", 0))
+    d.bias0, d.bias1 = bias0 or _lib.DebugBuf(None, 0), bias1 or _lib.DebugBuf(None, 0)
+    for k in ("M", "N", "K", "Z", "a_sm", "a_sk", "x_sz", "x_sk", "x_sn", "c_sz", "c_sm", "c_sn", "relu"):
+        setattr(d, k, p[k])
+    return d
+
+
+def wgrad_desc(p: dict, dY: _lib.DebugBuf, X: _lib.DebugBuf, out: _lib.DebugBuf) -> _lib.DebugWgradDesc:
+    d = _lib.DebugWgradDesc()
+    d.dY, d.X, d.out = _offset_buf(dY, p.get("y_base", 0)), _offset_buf(X, p.get("x_base", 0)), out
+    for j in range(min(p["ntaps"], _lib.DEBUG_MAX_TAPS)):
+        d.shift[j] = p["shift"][j]
+    for k in ("M", "K", "T", "R", "ntaps", "y_sz", "y_sm", "y_st", "x_sz", "x_sk", "x_st", "o_sm", "o_sk", "o_sj"):
+        setattr(d, k, p[k])
+    return d
+
+
+def debug_tap_gemm(p: dict, A: torch.Tensor, X: torch.Tensor, Cb: torch.Tensor, bias0=None, bias1=None) -> torch.Tensor:
+    """tap_gemm_kernel through launch_tap_gemm: writes the addressed elements of the flat ``Cb`` in place and returns it."""
+    d = tap_gemm_desc(p, debug_buf(A), debug_buf(X), debug_buf(Cb), debug_buf(bias0), debug_buf(bias1))
+    with torch.cuda.device(Cb.device):
+        _lib.check(_lib.lib().parrot_debug_tap_gemm(C.byref(d), stream_ptr(Cb.device)))
+    return Cb
+
+
+def debug_wgrad(p: dict, dY: torch.Tensor, X: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
+    """wgrad_kernel + wgrad_reduce_kernel as the model's wgrad() runs them; writes the addressed elements of the flat ``out``."""
+    d = wgrad_desc(p, debug_buf(dY), debug_buf(X), debug_buf(out))
+    lib = _lib.lib()
+    ws = _workspace(lib.parrot_debug_wgrad_workspace_bytes(p["R"], p["ntaps"], p["M"], p["K"]), out.device)
+    with torch.cuda.device(out.device):
+        _lib.check(lib.parrot_debug_wgrad(C.byref(d), dptr(ws), ws.numel(), stream_ptr(out.device)))
+    return out
+
+
+def debug_colsum(src: torch.Tensor, R: int, M: int, ld: int, out0: torch.Tensor, out1: Optional[torch.Tensor] = None, base: int = 0):
+    """colsum_part_kernel + colsum_final_kernel: out0[m] (and out1[m]) = sum_r src[base + r ld + m]."""
+    d = _lib.DebugColsumDesc(debug_buf(src, base), debug_buf(out0), debug_buf(out1), R, M, ld)
+    lib = _lib.lib()
+    ws = _workspace(lib.parrot_debug_colsum_workspace_bytes(R, M), src.device)
+    with torch.cuda.device(src.device):
+        _lib.check(lib.parrot_debug_colsum(C.byref(d), dptr(ws), ws.numel(), stream_ptr(src.device)))
+    return out0, out1
+
+
+def debug_bn_train(x: torch.Tensor, y: torch.Tensor, gamma, beta, run_mean, run_var, mean, invstd, training: bool, eps: float) -> None:
+    """bn_train_kernel on x (B, C, T): writes y, mean, invstd and -- training -- updates run_mean / run_var in place."""
+    B, C_, T = x.shape
+    d = _lib.DebugBnTrainDesc(*[debug_buf(t) for t in (x, y, gamma, beta, run_mean, run_var, mean, invstd)], B, C_, T, int(bool(training)), eps)
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.lib().parrot_debug_bn_train(C.byref(d), stream_ptr(x.device)))
+
+
+def debug_bn_relu_bwd(dy: torch.Tensor, x: torch.Tensor, dx: torch.Tensor, gamma, mean, invstd, dgamma=None, dbeta=None) -> None:
+    """bn_relu_bwd_kernel on (B, C, T): writes dx (which may be dy) and, when given, dgamma / dbeta."""
+    B, C_, T = x.shape
+    d = _lib.DebugBnBwdDesc(*[debug_buf(t) for t in (dy, x, dx, gamma, mean, invstd, dgamma, dbeta)], B, C_, T)
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.lib().parrot_debug_bn_relu_bwd(C.byref(d), stream_ptr(x.device)))

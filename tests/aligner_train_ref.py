@@ -20,6 +20,11 @@ SHAPES = {
     "S3": (1, 2, 24, 13, 32, 32, 1),
     "S4": (2, 33, 80, 13, 32, 32, 4),
     "S5": (17, 5, 24, 13, 32, 32, 2),  # more rows than one 16-row batch pass of the LSTM step kernels
+    # three trips of both LSTM k-loops with only some lanes in the last (128 + 4q < 144, 512 + 4q < 576); two block rows and a partial
+    # K pass in every conv and its gradients; 20 staging passes in the convs, 36 in dy_2
+    "S6": (2, 9, 24, 13, 144, 112, 3),
+    "S7": (3, 130, 24, 70, 32, 32, 6),  # three column blocks, the last 2 wide; a chunk boundary inside a batch row (B T = 390); V > 64
+    "S8": (3, 1, 24, 13, 32, 32, 1),    # T = 1: every side tap outside, one step of the recurrence
 }
 
 PARAM_KEYS = ([f"convs.{i}.conv.weight" for i in range(3)] + [f"convs.{i}.bnorm.weight" for i in range(3)]

@@ -136,6 +136,23 @@ def test_more_rows_than_one_batch_pass_of_the_lstm_kernels():
         _held(f"S5 random d {k}", grads[k], g32[k], g64[k])
 
 
+@pytest.mark.parametrize("shape, upstream", [("S6", "ctc"), ("S6", "random"), ("S7", "ctc"), ("S7", "random"), ("S8", "random")])
+def test_shapes_that_reach_the_second_trips_and_tile_edges(shape, upstream):
+    """S6: lstm_dim 144 and conv_dim 112 -- three trips of both LSTM k-loops with a partial last one, two block rows and a partial K
+    pass in every conv; S7: T = 130 and V = 70 -- three column blocks, a reduction chunk ending inside a batch row, a second block
+    of the Linear; S8: T = 1.  Logits and all 19 gradients under the rule of this file as it stands (the kernels on their own:
+    tests/test_gpu_aligner_train_kernels.py)."""
+    (l64, _, g64, _), (l32, _, g32, _) = _ref(shape, upstream)
+    logits, grads = _step(_model(shape).train(), shape, upstream)
+    assert logits.shape == l64.shape and len(grads) == 19
+    ratios = {"logits": _held(f"{shape} logits", logits, l32, l64)}
+    for k in TR.PARAM_KEYS:
+        assert grads[k] is not None and grads[k].shape == g64[k].shape, k
+        ratios[k] = _held(f"{shape} {upstream} d {k}", grads[k], g32[k], g64[k])
+    worst = max(ratios, key=ratios.get)
+    print(f"{shape} {upstream}: largest ratio {ratios[worst]:.2f} ({worst})")
+
+
 def test_buffers_after_one_and_three_forwards():
     shape = "S1"
     sd, mel, tokens, ml, tl = _case(shape)
