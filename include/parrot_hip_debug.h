@@ -50,7 +50,7 @@ int parrot_voc_debug_absmax(parrot_voc_t*, float* dst_dev);
  * enc_ptrs[1 + n] = encoder block n, enc_ptrs[1 + enc_layers] = encoder output (+ speaker); dec_ptrs[0] = length
  * regulator output + pe[L], dec_ptrs[1 + n] = decoder block n.  Pass NULL, NULL to switch it off. */
 int parrot_tte_debug_stages(parrot_tte_t*, float* const* enc_ptrs, float* const* dec_ptrs);
-/* Tests: the TTE's attention cores and its LayerNorm on their own, through the very launch code of the FFT block (csrc/host_tte.hip).
+/* Tests: the TTE's attention cores and its LayerNorm on their own, through the very launchers the FFT block calls (csrc/attn.h, tte_glue.h).
  * parrot_debug_attention: ctx (B, H hd, T) = softmax(q k^T sqrt(1 / hd) + key mask) v per (batch, head) of the channel-first
  * projections qkv (B, 3, H hd, T); valid (B, T) u8, non-zero = attend to this key (a row without a valid key: NaN throughout, as
  * torch).  core: 0 the three-kernel path (batched GEMM, masked softmax, batched GEMM over a (B, H, T, T) score tensor in ws; any
@@ -62,8 +62,8 @@ int parrot_debug_attention(const float* qkv, const uint8_t* valid, float* ctx, i
                            void* ws, size_t ws_bytes, void* stream);
 int parrot_debug_layernorm(const float* x, const float* gamma, const float* beta, float* y, int32_t B, int32_t C, int32_t T,
                            int32_t relu_in, void* stream);
-/* Tests: the TTE's duration, length-regulator and argmax / tie-guard kernels on their own, through the launch code of the model
- * (csrc/host_tte.hip), on caller-owned DEVICE buffers.  `status` (one device int, never NULL) takes the place of the handle's status
+/* Tests: the TTE's duration, length-regulator and argmax / tie-guard kernels on their own, through the launchers the model calls
+ * (csrc/tte_glue.h), on caller-owned DEVICE buffers.  `status` (one device int, never NULL) takes the place of the handle's status
  * word: 5 a non-finite log-duration of a real token or a non-finite logit, 6 a negative duration, 7 a duration at s >= src_len.
  * Null or empty arguments: PARROT_E_INVALID; more than 65535 rows or a dimension beyond PARROT_DEBUG_MAX_DIM: PARROT_E_UNSUPPORTED;
  * all before any launch.

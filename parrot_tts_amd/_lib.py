@@ -268,7 +268,7 @@ def check(code: int) -> None:
 
 
 E_RANGE, E_NONFINITE = -2, -6  # PARROT_E_RANGE, PARROT_E_NONFINITE of include/parrot_hip.h
-ST_NONFINITE = 5  # device status word of every handle kind: a non-finite output (csrc/kernels_misc.h, aligner.h, mel.h)
+ST_NONFINITE = 5  # device status word of every handle kind: a non-finite output (csrc/tte_glue.h, aligner.h, mel.h)
 
 
 def reraise(e: ParrotHipError, on_nonfinite=None):

@@ -1,5 +1,56 @@
-// attn.h -- batched fp32 MFMA GEMM for the attention score (Q K^T) and context (P V) products of the
-// torch MHA math path (reference modules/fft.py:56 -> F.multi_head_attention_forward).
+// attn.h -- the attention core softmax(q k^T sqrt(1/hd) + key mask) v of one FFT block on the channel-first (B, 3, D, T)
+// projections: ctx (B, D, T) (torch MHA math path, reference modules/fft.py:56 -> F.multi_head_attention_forward).
+// Three launch sequences compute it (ATTN_CORE_*); launch_attention_core() runs the one it is told to.
+// The kernel bodies are seen by the unit that instantiates them alone: the fp32-MFMA cores (bgemm_mfma_kernel,
+// softmax_mask_kernel, attn_fused_kernel) by tu_tte.hip (PARROT_TTE_TU), which defines launch_attention_core(); the flash core
+// by tu_attn.hip (PARROT_ATTN_FLASH_TU), built without the SLP vectoriser, which defines launch_attn_flash().
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <cmath>
+
+namespace parrot {
+
+// q / k / v / ctx are channel-first (hd, T) slices of the (B, 3, D, T) projection buffer / (B, D, T) context buffer.
+struct AttnParams {
+    const float* qkv;      // (B, 3, D, T)
+    const uint8_t* valid;  // (B, T) 1 = real key
+    float* ctx;            // (B, D, T)
+    int T, H, D, hd;
+    float alpha;
+};
+inline AttnParams attn_params(const float* qkv, const uint8_t* valid, float* ctx, int T, int H, int D) {
+    AttnParams p{};
+    p.qkv = qkv; p.valid = valid; p.ctx = ctx;
+    p.T = T; p.H = H; p.D = D; p.hd = D / H;
+    p.alpha = (float)std::sqrt(1.0 / (double)p.hd);
+    return p;
+}
+constexpr int ATTN_TMAX = 256;
+
+// `core` names the launch sequence (fft_block picks it; parrot_debug_attention runs any of them on its own):
+//   ATTN_CORE_THREE  bgemm_mfma_kernel -> softmax_mask_kernel -> bgemm_mfma_kernel through scores (B, H, T, T): any hd, any T
+//   ATTN_CORE_FUSED  attn_fused_kernel<128, 32>, one launch: hd = 128 and T <= ATTN_TMAX only
+//   ATTN_CORE_FLASH  attn_flash_kernel<hd>, online softmax on the fp16 split pipe: attn_flash_has(hd), any T
+// The caller has checked that the core takes the shape and that B H <= 65535 and B H T < 2^30 (grid rows; softmax_mask_kernel's
+// int row count); scores is only read by ATTN_CORE_THREE.
+enum { ATTN_CORE_THREE = 0, ATTN_CORE_FUSED = 1, ATTN_CORE_FLASH = 2 };
+hipError_t launch_attention_core(int core, const AttnParams& p, int B, float* scores, hipStream_t s);  // csrc/tu_tte.hip
+
+inline bool attn_flash_has(int hd) { return hd == 128 || hd == 64 || hd == 32 || hd == 16; }
+hipError_t launch_attn_flash(const AttnParams& p, int B, hipStream_t s);  // csrc/tu_attn.hip
+
+}  // namespace parrot
+
+#ifdef PARROT_TTE_TU
+#include "conv_mfma.h"  // (f32x16)
+#include "wave_reduce.h"
+
+namespace parrot {
+
+// ---------------------------------------------------------------------------------------------
+// Batched fp32 MFMA GEMM for the attention score (Q K^T) and context (P V) products of the three-kernel path.
 //
 //   C[z][m][n] = sum_k (alpha * A[z](k,m)) * B[z](k,n),  z = (batch, head)
 // Operands are addressed with explicit (k, m|n) strides so the same kernel serves
@@ -7,13 +58,95 @@
 //   context: A = v (m = head channel, k = t_k),                 B = P (n = t_q, k = t_k)
 // without any transposed copies.  Tiles are staged K-major in LDS ([k][m], [k][n], row stride 65 so the
 // transposing writes of the second form are bank-conflict free) and fed to v_mfma_f32_32x32x2_f32.
-#pragma once
-#include <hip/hip_runtime.h>
-#include "conv_mfma.h"
-#include "conv_split.h"
-#include "wave_reduce.h"
+// ---------------------------------------------------------------------------------------------
+struct BgemmParams {
+    const float* A;
+    const float* B;
+    float* C;
+    int M, N, K;
+    long a_sk, a_sm, b_sk, b_sn;      // element strides
+    long a_zb, a_zh, b_zb, b_zh;      // batch / head offsets
+    long c_zb, c_zh, ldc;
+    int H;
+    float alpha;
+};
 
-namespace parrot {
+static __global__ __launch_bounds__(256) void bgemm_mfma_kernel(const BgemmParams p) {
+    constexpr int KC = 32, RS = 65;
+    __shared__ float As[KC][RS];
+    __shared__ float Bs[KC][RS];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int wm = wave >> 1, wn = wave & 1, half = lane >> 5, l31 = lane & 31;
+    const int z = blockIdx.z, zb = z / p.H, zh = z - zb * p.H;
+    const int m0 = blockIdx.y * 64, n0 = blockIdx.x * 64;
+    const float* __restrict__ A = p.A + zb * p.a_zb + zh * p.a_zh;
+    const float* __restrict__ B = p.B + zb * p.b_zb + zh * p.b_zh;
+    f32x16 acc;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+
+    const bool a_kfast = (p.a_sk == 1), b_kfast = (p.b_sk == 1);
+    for (int k0 = 0; k0 < p.K; k0 += KC) {
+#pragma unroll
+        for (int i = 0; i < (KC * 64) / 256; ++i) {
+            const int idx = i * 256 + tid;
+            int kk, mm;
+            if (a_kfast) { mm = idx / KC; kk = idx % KC; } else { kk = idx / 64; mm = idx % 64; }
+            float v = 0.f;
+            if (k0 + kk < p.K && m0 + mm < p.M) v = A[(long)(k0 + kk) * p.a_sk + (long)(m0 + mm) * p.a_sm] * p.alpha;
+            As[kk][mm] = v;
+            int kb, nn;
+            if (b_kfast) { nn = idx / KC; kb = idx % KC; } else { kb = idx / 64; nn = idx % 64; }
+            float w = 0.f;
+            if (k0 + kb < p.K && n0 + nn < p.N) w = B[(long)(k0 + kb) * p.b_sk + (long)(n0 + nn) * p.b_sn];
+            Bs[kb][nn] = w;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int ks = 0; ks < KC; ks += 2) {
+            const float a = As[ks + half][wm * 32 + l31];
+            const float b = Bs[ks + half][wn * 32 + l31];
+            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, acc, 0, 0, 0);
+        }
+        __syncthreads();
+    }
+    float* __restrict__ C = p.C + zb * p.c_zb + zh * p.c_zh;
+    const int n = n0 + wn * 32 + l31;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const int m = m0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
+        if (m < p.M && n < p.N) C[(long)m * p.ldc + n] = acc[r];
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// Row softmax of attention scores with a key-padding mask (torch MHA math path, Q3):
+// P[r, :] = softmax(S[r, :] + (-inf where key masked)).  One wave per row, wave-shuffle reductions.
+// rows = B*H*T, row r belongs to batch r / (H*T).  key_valid (B,T) u8 1 = attend.
+// ---------------------------------------------------------------------------------------------
+static __global__ __launch_bounds__(256) void softmax_mask_kernel(float* __restrict__ s, const uint8_t* __restrict__ key_valid, int rows,
+                                                           int T, int HT) {
+    const int lane = threadIdx.x & 63;
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const int b = row / HT;
+    float* sr = s + (size_t)row * T;
+    const uint8_t* kv = key_valid + (size_t)b * T;
+    float mx = -INFINITY;
+    for (int t = lane; t < T; t += 64) {
+        const float v = kv[t] ? sr[t] : -INFINITY;
+        mx = fmaxf(mx, v);
+    }
+    mx = wave_max(mx);
+    float sum = 0.f;
+    for (int t = lane; t < T; t += 64) {
+        const float e = kv[t] ? expf(sr[t] - mx) : 0.f;
+        sr[t] = e;
+        sum += e;
+    }
+    sum = wave_sum(sum);
+    for (int t = lane; t < T; t += 64) sr[t] = sr[t] / sum;
+}
 
 // ---------------------------------------------------------------------------------------------
 // Fused attention core for sequences of <= 256 steps: scores, key-padding softmax and context in ONE launch per
@@ -23,16 +156,6 @@ namespace parrot {
 //   phase 1  S[tq][tk] = sum_c (alpha q[c][tq]) k[c][tk]  -> LDS, 64 x T            (32x32 tiles dealt round-robin to waves)
 //   softmax  P = softmax(S + key mask) per query row, in LDS                        (16 rows per wave)
 //   phase 2  ctx[c][tq] = sum_tk v[c][tk] P[tq][tk]                                 (wave w: channels 32w.., both query tiles)
-// q / k / v / ctx are channel-first (hd, T) slices of the (B, 3, D, T) projection buffer / (B, D, T) context buffer.
-struct AttnParams {
-    const float* qkv;      // (B, 3, D, T)
-    const uint8_t* valid;  // (B, T) 1 = real key
-    float* ctx;            // (B, D, T)
-    int T, H, D, hd;
-    float alpha;
-};
-constexpr int ATTN_TMAX = 256;
-
 template <int HD, int QT>
 __global__ __launch_bounds__(256) void attn_fused_kernel(const AttnParams p) {
     constexpr int MT = QT / 32;    // query tiles of 32 per workgroup (QT = 32: 33 KiB of LDS -> 4 workgroups per CU)
@@ -142,6 +265,15 @@ __global__ __launch_bounds__(256) void attn_fused_kernel(const AttnParams p) {
         }
     }
 }
+
+}  // namespace parrot
+
+#endif  // PARROT_TTE_TU
+
+#ifdef PARROT_ATTN_FLASH_TU
+#include "conv_split.h"  // (SchF16x3, mfma32; conv_mfma.h: f32x16, ensure_dyn_lds)
+
+namespace parrot {
 
 // ---------------------------------------------------------------------------------------------
 // Flash-style attention core for ANY sequence length on the fp16 split pipe (SchF16x3: 3 fp16 MFMAs per product group,
@@ -371,7 +503,6 @@ __global__ __launch_bounds__(256, 2) void attn_flash_kernel(const AttnParams p) 
     }
 }
 
-inline bool attn_flash_has(int hd) { return hd == 128 || hd == 64 || hd == 32 || hd == 16; }
 template <int HD>
 inline hipError_t launch_attn_flash_t(const AttnParams& p, int B, hipStream_t s) {
     constexpr int MT = (HD + 31) / 32;
@@ -385,6 +516,7 @@ inline hipError_t launch_attn_flash_t(const AttnParams& p, int B, hipStream_t s)
     hipLaunchKernelGGL(kern, dim3((p.T + 127) / 128, B * p.H), dim3(256), lds, s, p);
     return hipGetLastError();
 }
-hipError_t launch_attn_flash(const AttnParams& p, int B, hipStream_t s);  // csrc/tu_attn.hip
 
 }  // namespace parrot
+
+#endif  // PARROT_ATTN_FLASH_TU

@@ -1,13 +1,14 @@
-// host_tte.hip -- the text-to-unit model: create, the FFT block, encode / decode with the tie guard, the loss and the stand-alone
-// length regulator.
+// host_tte.hip -- the text-to-unit model: create, the FFT block, encode / decode with the tie guard, and the stand-alone length
+// regulator.  Plain host code: every kernel is reached through the launchers of attn.h and tte_glue.h (tu_tte.hip), the same ones
+// the parrot_debug_* entry points (host_tte_debug.hip) call.  The loss is host_tte_loss.hip.
 #include "host_common.h"
 
 #include <algorithm>
-#include <cmath>
+#include <cstdlib>
 #include <vector>
 
 #include "attn.h"
-#include "kernels_misc.h"
+#include "tte_glue.h"
 
 using namespace parrot;
 
@@ -40,7 +41,7 @@ struct parrot_tte {
     float *head_w = nullptr, *head_b = nullptr;
     // (one set per decoder lane -- parrot_tte_decode_rows: row groups of one batch may decode concurrently on several streams --
     //  laid out back to back: lane l's list / statistics / refined logits start at l x the per-lane size)
-    static constexpr int LANES = 1;
+    static constexpr int LANES = TTE_LANES;
     int *glist = nullptr, *gstat = nullptr;
     int lanes_used = 1;  // bit l: lane l took part in the last decoded batch (host-side bookkeeping of the statistics readers)
     float guard = 1e-4f;
@@ -246,65 +247,6 @@ static ConvOpts rows_of(const int32_t* len) {
     o.rows.len = len;
     return o;
 }
-static int layernorm(const float* x, const float* g, const float* b, float* y, int B, int C, int T, int relu_in, hipStream_t s) {
-    hipLaunchKernelGGL(layernorm_cf_kernel<16>, dim3((T + 63) / 64, B), dim3(16 * 64), 0, s, x, g, b, y, C, T, 1e-5f, relu_in);
-    HIP_TRY(hipGetLastError());
-    return PARROT_OK;
-}
-
-// The attention core softmax(q k^T sqrt(1/hd) + key mask) v of one FFT block on the channel-first (B, 3, D, T) projections:
-// ctx (B, D, T).  `core` names the launch sequence (fft_block picks it; parrot_debug_attention runs any of them on its own):
-//   ATTN_CORE_THREE  bgemm_mfma_kernel -> softmax_mask_kernel -> bgemm_mfma_kernel through scores (B, H, T, T): any hd, any T
-//   ATTN_CORE_FUSED  attn_fused_kernel<128, 32>, one launch: hd = 128 and T <= ATTN_TMAX only
-//   ATTN_CORE_FLASH  attn_flash_kernel<hd>, online softmax on the fp16 split pipe: attn_flash_has(hd), any T
-// The caller has checked that the core takes the shape; scores is only read by ATTN_CORE_THREE.
-enum { ATTN_CORE_THREE = 0, ATTN_CORE_FUSED = 1, ATTN_CORE_FLASH = 2 };
-static int attention_core(int core, const float* qkv, const uint8_t* valid, float* ctx, float* scores, int B, int T, int H, int D,
-                          hipStream_t s) {
-    const int hd = D / H;
-    const long DT = (long)D * T;
-    if (core == ATTN_CORE_FLASH) {  // any T, online softmax, no score tensor (attn.h: attn_flash_kernel)
-        AttnParams p{};
-        p.qkv = qkv; p.valid = valid; p.ctx = ctx;
-        p.T = T; p.H = H; p.D = D; p.hd = hd;
-        p.alpha = (float)std::sqrt(1.0 / (double)hd);
-        HIP_TRY(launch_attn_flash(p, B, s));
-    } else if (core == ATTN_CORE_FUSED) {  // scores, softmax and context in one launch (attn.h)
-        AttnParams p{};
-        p.qkv = qkv; p.valid = valid; p.ctx = ctx;
-        p.T = T; p.H = H; p.D = D; p.hd = hd;
-        p.alpha = (float)std::sqrt(1.0 / (double)hd);
-        const size_t lds = (size_t)32 * (((T + 31) / 32) * 32 + 1) * sizeof(float);  // 32-query tiles (33 KiB at T = 256: no opt-in needed)
-        hipLaunchKernelGGL((attn_fused_kernel<128, 32>), dim3((T + 31) / 32, B * H), dim3(256), lds, s, p);
-        HIP_TRY(hipGetLastError());
-    } else {
-    {   // scores[b,h][tq][tk] = sum_c (q[c][tq] * sqrt(1/hd)) * k[c][tk]
-        BgemmParams p{};
-        p.A = qkv; p.B = qkv + DT; p.C = scores;
-        p.M = T; p.N = T; p.K = hd;
-        p.a_sk = T; p.a_sm = 1; p.b_sk = T; p.b_sn = 1;
-        p.a_zb = 3 * DT; p.a_zh = (long)hd * T; p.b_zb = 3 * DT; p.b_zh = (long)hd * T;
-        p.c_zb = (long)H * T * T; p.c_zh = (long)T * T; p.ldc = T; p.H = H;
-        p.alpha = (float)std::sqrt(1.0 / (double)hd);
-        hipLaunchKernelGGL(bgemm_mfma_kernel, dim3((T + 63) / 64, (T + 63) / 64, B * H), dim3(256), 0, s, p);
-        HIP_TRY(hipGetLastError());
-    }
-    hipLaunchKernelGGL(softmax_mask_kernel, dim3((B * H * T + 3) / 4), dim3(256), 0, s, scores, valid, B * H * T, T, H * T);
-    HIP_TRY(hipGetLastError());
-    {   // ctx[b][h*hd + c][tq] = sum_tk v[c][tk] * P[tq][tk]
-        BgemmParams p{};
-        p.A = qkv + 2 * DT; p.B = scores; p.C = ctx;
-        p.M = hd; p.N = T; p.K = T;
-        p.a_sk = 1; p.a_sm = T; p.b_sk = 1; p.b_sn = T;
-        p.a_zb = 3 * DT; p.a_zh = (long)hd * T; p.b_zb = (long)H * T * T; p.b_zh = (long)T * T;
-        p.c_zb = DT; p.c_zh = (long)hd * T; p.ldc = T; p.H = H;
-        p.alpha = 1.0f;
-        hipLaunchKernelGGL(bgemm_mfma_kernel, dim3((T + 63) / 64, (hd + 63) / 64, B * H), dim3(256), 0, s, p);
-        HIP_TRY(hipGetLastError());
-    }
-    }
-    return PARROT_OK;
-}
 
 // FFTBlock.forward (fft.py:94-100): x -> out (may alias x).  valid (B,T) u8: 1 = attend to this key.
 // row_len (B) i32 device, nullable: ROW-EXACT mode -- row b holds row_len[b] real positions and every conv applies its zero padding
@@ -313,7 +255,7 @@ static int attention_core(int core, const float* qkv, const uint8_t* valid, floa
 static int fft_block(const parrot_tte* t, const FftLayer* L, TteScratch& w, float* x, const uint8_t* valid, int B, int T, hipStream_t s,
                      const int32_t* row_len = nullptr) {
     const int D = t->cfg.d_model, H = L->heads, hd = D / H;
-    TRY(layernorm(x, L->an_w, L->an_b, w.n, B, D, T, 0, s));
+    HIP_TRY(launch_layernorm(x, L->an_w, L->an_b, w.n, B, D, T, 0, s));
     if (L->merged) {
         TRY(conv_launch(L->qkv.get(), w.n, nullptr, w.qkv2, B, T, EPI_STORE, 1.f, s));
     } else {
@@ -323,58 +265,17 @@ static int fft_block(const parrot_tte* t, const FftLayer* L, TteScratch& w, floa
     // the selection rule: a flash handle takes attn_flash_kernel at any T; the fp32-MFMA handles take the fused core where it
     // fits (hd = 128, T <= 256) and the three-kernel path everywhere else
     const int core = t->flash ? ATTN_CORE_FLASH : (T <= ATTN_TMAX && hd == 128) ? ATTN_CORE_FUSED : ATTN_CORE_THREE;
-    TRY(attention_core(core, w.qkv2, valid, w.ctx, w.scores, B, T, H, D, s));
+    HIP_TRY(launch_attention_core(core, attn_params(w.qkv2, valid, w.ctx, T, H, D), B, w.scores, s));
     if (L->merged) {
         TRY(conv_launch(L->wo.get(), w.ctx, x, w.h, B, T, EPI_STORE, 1.f, s));        // h = x + attn
     } else {
         TRY(conv_launch(L->out_proj.get(), w.ctx, nullptr, w.o, B, T, EPI_STORE, 1.f, s));
         TRY(conv_launch(L->wo.get(), w.o, x, w.h, B, T, EPI_STORE, 1.f, s));          // h = x + attn
     }
-    TRY(layernorm(w.h, L->cn_w, L->cn_b, w.n, B, D, T, 0, s));
+    HIP_TRY(launch_layernorm(w.h, L->cn_w, L->cn_b, w.n, B, D, T, 0, s));
     // (a 1x1 conv has no neighbours to leak from: only the k > 1 convs take the per-row ends)
     TRY(conv_launch(L->conv1.get(), w.n, nullptr, w.f, B, T, EPI_STORE, 1.f, s, rows_of(t->cfg.ffn_k1 > 1 ? row_len : nullptr)));  // relu fused
     TRY(conv_launch(L->conv2.get(), w.f, w.h, x, B, T, EPI_STORE, 1.f, s, rows_of(t->cfg.ffn_k2 > 1 ? row_len : nullptr)));      // out = h + ffn
-    return PARROT_OK;
-}
-
-// The launches of the duration / length-regulator / argmax glue kernels (kernels_misc.h), one helper each: the model paths below and
-// the parrot_debug_* entry points (tests) run the same launch code.
-static int launch_durations(const float* ld_raw, const uint8_t* src_valid, float* log_dur, int64_t* dur, int32_t* cum, int32_t* out_len, int B,
-                            int S, const int32_t* src_len, int* err, hipStream_t s) {
-    hipLaunchKernelGGL(duration_kernel, dim3(B), dim3(256), 0, s, ld_raw, src_valid, log_dur, dur, cum, out_len, S, src_len, err);
-    HIP_TRY(hipGetLastError());
-    return PARROT_OK;
-}
-static int launch_dur_prefix(const int64_t* dur, int32_t* cum, int32_t* out_len, int B, int S, int* err, const int32_t* src_len, hipStream_t s) {
-    hipLaunchKernelGGL(dur_prefix_kernel, dim3(B), dim3(256), 0, s, dur, cum, out_len, S, err, src_len);
-    HIP_TRY(hipGetLastError());
-    return PARROT_OK;
-}
-static int launch_length_regulate(const float* enc, const int32_t* cum, const int32_t* out_len, const float* pe, float* y, uint8_t* tgt_mask, int B,
-                                  int S, int L, int D, int* gstat, int gstat_reset, int row_exact, int pe_stride, hipStream_t s) {
-    hipLaunchKernelGGL(length_regulate_kernel, dim3((L + 63) / 64, B), dim3(256), 0, s, enc, cum, out_len, pe, y, tgt_mask, S, L, D, gstat,
-                       gstat_reset, row_exact, pe_stride);
-    HIP_TRY(hipGetLastError());
-    return PARROT_OK;
-}
-// the tie guard's fp64 re-evaluation (tie_guard_refine_kernel): x == NULL switches it off
-struct RefineArgs {
-    const float *x = nullptr, *hwt = nullptr, *hb = nullptr;                     // (B, D, L), (D, V), (V) nullable
-    const float *f = nullptr, *h = nullptr, *w2t = nullptr, *b2 = nullptr;       // deep form (f != NULL): (B, F, L), (B, D, L), (F, D), (D) nullable
-    int D = 0, F = 0;
-    float* gref = nullptr;
-};
-// argmax + tie guard: gstat = {count, ids changed, min margin (float bits), first list entry of this row group}; glist / gstat NULL: ids only
-static int launch_argmax_guard(const float* logits, int64_t* ids, int B, int V, int L, int* err, float guard, int* glist, int* gstat, int row0,
-                               const RefineArgs& r, hipStream_t s) {
-    hipLaunchKernelGGL(argmax_cf_kernel, dim3((L + 63) / 64, B), dim3(64 * ARGMAX_WAVES), 0, s, logits, ids, V, L, err, guard, glist, gstat, row0);
-    HIP_TRY(hipGetLastError());
-    if (gstat && r.x) {  // re-evaluate the head of the low-margin positions in fp64 (workgroups beyond the count exit at once)
-        const bool deep = r.f != nullptr;
-        hipLaunchKernelGGL(tie_guard_refine_kernel, dim3(TIE_GUARD_MAX), dim3(256), (size_t)(r.D + (deep ? r.F : 0)) * sizeof(double), s, r.x, r.hwt,
-                           r.hb, ids, r.D, V, L, glist, gstat, r.f, r.h, r.w2t, r.b2, r.F, r.gref, row0);
-        HIP_TRY(hipGetLastError());
-    }
     return PARROT_OK;
 }
 
@@ -401,9 +302,7 @@ static int tte_encode_rows(parrot_tte_t* t, const int64_t* phones, const uint8_t
     st.out_len += row0;
     const int D = c.d_model;
     // pe[S] of the padded batch (quirk Q1 / Q7), or -- row-exact -- pe[src_len[b]]: what the row's own B = 1 run adds (fft.py:18)
-    hipLaunchKernelGGL(tte_embed_kernel, dim3((S + 63) / 64, (D + 63) / 64, B), dim3(256), 0, s, phones, t->tok, t->pe, src_len,
-                       w.x, S, D, c.vocab, t->err);
-    HIP_TRY(hipGetLastError());
+    HIP_TRY(launch_tte_embed(phones, t->tok, t->pe, src_len, w.x, B, S, D, c.vocab, t->err, s));
     auto dbg = [&](const std::vector<float*>& v, size_t idx, const float* src, size_t n) -> int {
         if (idx < v.size() && v[idx]) HIP_TRY(hipMemcpyAsync(v[idx] + (size_t)row0 * D * S, src, n * sizeof(float), hipMemcpyDeviceToDevice, s));
         return PARROT_OK;
@@ -413,22 +312,17 @@ static int tte_encode_rows(parrot_tte_t* t, const int64_t* phones, const uint8_t
         TRY(fft_block(t, t->enc[n].get(), w, w.x, src_mask, B, S, s, src_len));
         TRY(dbg(t->dbg_enc, 1 + n, w.x, (size_t)B * D * S));
     }
-    if (t->spk) {
-        const size_t total = (size_t)B * D * S;
-        hipLaunchKernelGGL(add_channel_vec_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, w.x, speaker, t->spk, D, S,
-                           c.n_speaker, total, t->err);
-        HIP_TRY(hipGetLastError());
-    }
+    if (t->spk) HIP_TRY(launch_add_channel_vec(w.x, speaker, t->spk, B, D, S, c.n_speaker, t->err, s));
     TRY(dbg(t->dbg_enc, 1 + t->enc.size(), w.x, (size_t)B * D * S));
     HIP_TRY(hipMemcpyAsync(st.enc_out, w.x, (size_t)B * D * S * sizeof(float), hipMemcpyDeviceToDevice, s));
     // duration predictor (duration.py:29-48): conv -> relu -> LN -> conv(pad 1) -> relu -> LN -> linear
     const int NF = c.dp_filter;
     TRY(conv_launch(t->dp0.get(), w.x, nullptr, w.f, B, S, EPI_STORE, 1.f, s, rows_of(src_len)));
-    TRY(layernorm(w.f, t->ln0_w, t->ln0_b, w.n, B, NF, S, 1, s));
+    HIP_TRY(launch_layernorm(w.f, t->ln0_w, t->ln0_b, w.n, B, NF, S, 1, s));
     TRY(conv_launch(t->dp1.get(), w.n, nullptr, w.f, B, S, EPI_STORE, 1.f, s, rows_of(src_len)));
-    TRY(layernorm(w.f, t->ln1_w, t->ln1_b, w.n, B, NF, S, 1, s));
+    HIP_TRY(launch_layernorm(w.f, t->ln1_w, t->ln1_b, w.n, B, NF, S, 1, s));
     TRY(conv_launch(t->dp_proj.get(), w.n, nullptr, w.o, B, S, EPI_STORE, 1.f, s));  // (B,1,S)
-    TRY(launch_durations(w.o, src_mask, log_dur, dur, st.cum, st.out_len, B, S, src_len, t->err, s));
+    HIP_TRY(launch_durations(w.o, src_mask, log_dur, dur, st.cum, st.out_len, B, S, src_len, t->err, s));
     HIP_TRY(hipMemcpyAsync(out_lens, st.out_len, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
     return PARROT_OK;
 }
@@ -474,8 +368,8 @@ static int tte_decode_rows(parrot_tte_t* t, int32_t Bfull, int32_t S, int32_t L,
     int* const glist = t->glist ? t->glist + (size_t)lane * 2 * TIE_GUARD_MAX : nullptr;
     float* const gref = t->gref ? t->gref + (size_t)lane * TIE_GUARD_MAX * V : nullptr;
     t->lanes_used = (new_batch ? 0 : t->lanes_used) | (1 << lane);
-    TRY(launch_length_regulate(st.enc_out + (size_t)row0 * D * S, st.cum + (size_t)row0 * S, st.out_len + row0, t->pe, w.x, tgt_mask, B, S, L, D,
-                               t->guard > 0.f ? gstat : nullptr, guard_restart ? 1 : 0, row_exact ? 1 : 0, -1, s));
+    HIP_TRY(launch_length_regulate(st.enc_out + (size_t)row0 * D * S, st.cum + (size_t)row0 * S, st.out_len + row0, t->pe, w.x, tgt_mask, B, S, L, D,
+                                   t->guard > 0.f ? gstat : nullptr, guard_restart ? 1 : 0, row_exact ? 1 : 0, -1, s));
     const uint8_t* const valid = key_mask ? key_mask : tgt_mask;
     auto dbg = [&](size_t idx, const float* src, size_t n) -> int {
         if (idx < t->dbg_dec.size() && t->dbg_dec[idx])
@@ -497,12 +391,9 @@ static int tte_decode_rows(parrot_tte_t* t, int32_t Bfull, int32_t S, int32_t L,
         r.x = w.x; r.hwt = t->head_w; r.hb = t->head_b;
         r.f = deep ? w.f : nullptr; r.h = deep ? w.h : nullptr; r.w2t = t->last_w2t; r.b2 = t->last_b2;
         r.D = D; r.F = c.n_filter_ffn; r.gref = gref;
-        TRY(launch_argmax_guard(w.logits, ids, B, V, L, t->err, t->guard, on ? glist : nullptr, on ? gstat : nullptr, row0, r, s));
+        HIP_TRY(launch_argmax_guard(w.logits, ids, B, V, L, t->err, t->guard, on ? glist : nullptr, on ? gstat : nullptr, row0, r, s));
     }
-    if (logits) {
-        hipLaunchKernelGGL(transpose_cf_to_cl_kernel, dim3((L + 63) / 64, (V + 63) / 64, B), dim3(256), 0, s, w.logits, logits, V, L);
-        HIP_TRY(hipGetLastError());
-    }
+    if (logits) HIP_TRY(launch_transpose_cf_to_cl(w.logits, logits, B, V, L, s));
     return PARROT_OK;
 }
 extern "C" int parrot_tte_decode(parrot_tte_t* t, int32_t B, int32_t S, int32_t L, int32_t row_exact, int64_t* ids, uint8_t* tgt_mask,
@@ -527,7 +418,7 @@ extern "C" int parrot_tte_set_durations(parrot_tte_t* t, const int64_t* dur, int
     TteState st = tte_state(t, sa, B, S);
     if (!sa.ok) return fail(PARROT_E_NOMEM, "tte_set_durations: state too small");
     if (poison_word()) TRY(poison(out_lens, (size_t)B * sizeof(int32_t), s));
-    TRY(launch_dur_prefix(dur, st.cum, st.out_len, B, S, t->err, src_len, s));
+    HIP_TRY(launch_dur_prefix(dur, st.cum, st.out_len, B, S, t->err, src_len, s));
     HIP_TRY(hipMemcpyAsync(out_lens, st.out_len, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
     return PARROT_OK;
 }
@@ -542,216 +433,6 @@ extern "C" int parrot_tte_decode_masked(parrot_tte_t* t, int32_t B, int32_t S, i
     }
     return tte_decode_rows(t, B, S, L, 0, B, ids, nullptr, logits, state, state_bytes, ws, ws_bytes, stream, 0, true, true, row_exact != 0,
                            key_mask);
-}
-
-// ModelLoss (modules/loss.py:5-21): loss_rows_kernel + loss_reduce_kernel (kernels_misc.h); with the gradient, loss_count_kernel first
-static size_t loss_ws(Arena& a, int32_t N, double** nll, LossCounts** cnt, int64_t** bad) {
-    const size_t nblk = (size_t)std::max((N + LOSS_WAVES - 1) / LOSS_WAVES, 1);
-    *nll = a.take<double>(nblk);
-    *cnt = a.take<LossCounts>(nblk);
-    *bad = a.take<int64_t>(nblk);
-    return align_up(a.off, 256);
-}
-extern "C" size_t parrot_tte_loss_workspace_bytes(int32_t N) {
-    if (N < 0) return 0;
-    Arena a(nullptr, 0);
-    double* nll;
-    LossCounts* cnt;
-    int64_t* bad;
-    return loss_ws(a, N, &nll, &cnt, &bad);
-}
-extern "C" int parrot_tte_loss(const float* logits, const int64_t* targets, int32_t N, int32_t V, int64_t ignore_index, const float* log_dur,
-                               const int64_t* dur, const uint8_t* src_mask, int32_t n_src, double* out, float* losses, void* ws, size_t ws_bytes,
-                               void* stream) {
-    if (!logits || !targets || !log_dur || !dur || !src_mask || !out || !ws) return fail(PARROT_E_INVALID, "tte_loss: null argument");
-    if (N <= 0 || V <= 0 || n_src < 0) return fail(PARROT_E_INVALID, "tte_loss: empty logits or negative size");
-    hipStream_t s = (hipStream_t)stream;
-    Arena a(ws, ws_bytes);
-    double* nll;
-    LossCounts* cnt;
-    int64_t* bad;
-    (void)loss_ws(a, N, &nll, &cnt, &bad);
-    if (!a.ok) return fail(PARROT_E_NOMEM, "tte_loss: workspace too small");
-    if (poison_word()) {
-        TRY(poison(ws, ws_bytes, s));
-        TRY(poison(out, 8 * sizeof(double), s));
-        TRY(poison(losses, 3 * sizeof(float), s));
-    }
-    const int nblk = (N + LOSS_WAVES - 1) / LOSS_WAVES;
-    hipLaunchKernelGGL(loss_rows_kernel<false>, dim3(nblk), dim3(64 * LOSS_WAVES), 0, s, logits, targets, N, V, ignore_index, nll, cnt, bad, nullptr, nullptr);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(loss_reduce_kernel, dim3(1), dim3(LOSS_REDUCE), 0, s, nll, cnt, bad, nblk, log_dur, dur, src_mask, n_src, out, losses);
-    HIP_TRY(hipGetLastError());
-    return PARROT_OK;
-}
-
-// The same with the gradient (train.py:72-85): count + duration gradient, rows + logit gradient, the forward's reduction
-static size_t loss_grad_ws(Arena& a, int32_t N, double** nll, LossCounts** cnt, int64_t** bad, LossScale** scale) {
-    (void)loss_ws(a, N, nll, cnt, bad);
-    *scale = a.take<LossScale>(1);
-    return align_up(a.off, 256);
-}
-extern "C" size_t parrot_tte_loss_grad_workspace_bytes(int32_t N) {
-    if (N < 0) return 0;
-    Arena a(nullptr, 0);
-    double* nll;
-    LossCounts* cnt;
-    int64_t* bad;
-    LossScale* scale;
-    return loss_grad_ws(a, N, &nll, &cnt, &bad, &scale);
-}
-extern "C" int parrot_tte_loss_grad(const float* logits, const int64_t* targets, int32_t N, int32_t V, int64_t ignore_index, const float* log_dur,
-                                    const int64_t* dur, const uint8_t* src_mask, int32_t n_src, const double* weights, double* out, float* losses,
-                                    float* grad_logits, float* grad_log_dur, void* ws, size_t ws_bytes, void* stream) {
-    if (!logits || !targets || !log_dur || !dur || !src_mask || !out || !ws) return fail(PARROT_E_INVALID, "tte_loss_grad: null argument");
-    if (N <= 0 || V <= 0 || n_src < 0) return fail(PARROT_E_INVALID, "tte_loss_grad: empty logits or negative size");
-    if (!grad_logits && !grad_log_dur) return fail(PARROT_E_INVALID, "tte_loss_grad: both gradients null (parrot_tte_loss is the forward alone)");
-    if (grad_logits == logits || grad_log_dur == log_dur) return fail(PARROT_E_INVALID, "tte_loss_grad: a gradient must not alias its input");
-    hipStream_t s = (hipStream_t)stream;
-    Arena a(ws, ws_bytes);
-    double* nll;
-    LossCounts* cnt;
-    int64_t* bad;
-    LossScale* scale;
-    (void)loss_grad_ws(a, N, &nll, &cnt, &bad, &scale);
-    if (!a.ok) return fail(PARROT_E_NOMEM, "tte_loss_grad: workspace too small");
-    if (poison_word()) {
-        TRY(poison(ws, ws_bytes, s));
-        TRY(poison(out, 8 * sizeof(double), s));
-        TRY(poison(losses, 3 * sizeof(float), s));
-        TRY(poison(grad_logits, (size_t)N * V * sizeof(float), s));
-        TRY(poison(grad_log_dur, (size_t)n_src * sizeof(float), s));
-    }
-    const int nblk = (N + LOSS_WAVES - 1) / LOSS_WAVES;
-    hipLaunchKernelGGL(loss_count_kernel, dim3(1), dim3(LOSS_REDUCE), 0, s, targets, N, V, ignore_index, log_dur, dur, src_mask, n_src, weights, scale,
-                       grad_log_dur);
-    HIP_TRY(hipGetLastError());
-    if (grad_logits)
-        hipLaunchKernelGGL(loss_rows_kernel<true>, dim3(nblk), dim3(64 * LOSS_WAVES), 0, s, logits, targets, N, V, ignore_index, nll, cnt, bad, scale,
-                           grad_logits);
-    else
-        hipLaunchKernelGGL(loss_rows_kernel<false>, dim3(nblk), dim3(64 * LOSS_WAVES), 0, s, logits, targets, N, V, ignore_index, nll, cnt, bad, nullptr,
-                           nullptr);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(loss_reduce_kernel, dim3(1), dim3(LOSS_REDUCE), 0, s, nll, cnt, bad, nblk, log_dur, dur, src_mask, n_src, out, losses);
-    HIP_TRY(hipGetLastError());
-    return PARROT_OK;
-}
-
-// ---------------------------------------------------------------------------------------------
-// The attention cores and the LayerNorm on their own (tests: include/parrot_hip_debug.h).  Both run the functions fft_block runs.
-// ---------------------------------------------------------------------------------------------
-static float* debug_attention_ws(Arena& a, int B, int T, int H, int core) {
-    float* scores = core == ATTN_CORE_THREE ? a.take<float>((size_t)B * H * T * T) : nullptr;
-    a.take<char>(1);  // (never empty: the fused and flash cores take no workspace, and the entry refuses a null one)
-    return scores;
-}
-extern "C" size_t parrot_debug_attention_workspace_bytes(int32_t B, int32_t T, int32_t H, int32_t core) {
-    if (B <= 0 || T <= 0 || H <= 0 || core < ATTN_CORE_THREE || core > ATTN_CORE_FLASH) return 0;
-    Arena a(nullptr, 0);
-    (void)debug_attention_ws(a, B, T, H, core);
-    return align_up(a.off, 256);
-}
-extern "C" int parrot_debug_attention(const float* qkv, const uint8_t* valid, float* ctx, int32_t B, int32_t T, int32_t H, int32_t hd,
-                                      int32_t core, void* ws, size_t ws_bytes, void* stream) {
-    if (!qkv || !valid || !ctx || !ws) return fail(PARROT_E_INVALID, "debug_attention: null argument");
-    if (B <= 0 || T <= 0 || H <= 0 || hd <= 0) return fail(PARROT_E_INVALID, "debug_attention: non-positive size");
-    if (core < ATTN_CORE_THREE || core > ATTN_CORE_FLASH) return fail(PARROT_E_INVALID, "debug_attention: core in 0 .. 2");
-    if ((long)B * H > 65535 || (long)B * H * T >= (1L << 30) || (long)H * hd >= (1L << 30))  // (grid rows; softmax_mask_kernel's int row count)
-        return fail(PARROT_E_UNSUPPORTED, "debug_attention: B H > 65535, or B H T / H hd beyond the kernels' 32-bit indices");
-    if (core == ATTN_CORE_FUSED && (hd != 128 || T > ATTN_TMAX))
-        return fail(PARROT_E_UNSUPPORTED, "debug_attention: the fused core takes hd = 128 and T <= 256 only");
-    if (core == ATTN_CORE_FLASH && !attn_flash_has(hd)) return fail(PARROT_E_UNSUPPORTED, "debug_attention: the flash core takes hd in {16, 32, 64, 128} only");
-    hipStream_t s = (hipStream_t)stream;
-    Arena a(ws, ws_bytes);
-    float* scores = debug_attention_ws(a, B, T, H, core);
-    if (!a.ok) return fail(PARROT_E_NOMEM, "debug_attention: workspace too small");
-    if (poison_word()) {
-        TRY(poison(ws, ws_bytes, s));
-        TRY(poison(ctx, (size_t)B * H * hd * T * sizeof(float), s));
-    }
-    return attention_core(core, qkv, valid, ctx, scores, B, T, H, H * hd, s);
-}
-extern "C" int parrot_debug_layernorm(const float* x, const float* gamma, const float* beta, float* y, int32_t B, int32_t C, int32_t T,
-                                      int32_t relu_in, void* stream) {
-    if (!x || !gamma || !beta || !y) return fail(PARROT_E_INVALID, "debug_layernorm: null argument");
-    if (B <= 0 || C <= 0 || T <= 0) return fail(PARROT_E_INVALID, "debug_layernorm: non-positive size");
-    if (B > 65535) return fail(PARROT_E_UNSUPPORTED, "debug_layernorm: B > 65535 (one grid row per batch row)");
-    hipStream_t s = (hipStream_t)stream;
-    if (poison_word()) TRY(poison(y, (size_t)B * C * T * sizeof(float), s));
-    return layernorm(x, gamma, beta, y, B, C, T, relu_in != 0, s);
-}
-
-// ---------------------------------------------------------------------------------------------
-// The duration, length-regulator and argmax / tie-guard kernels on their own (tests: include/parrot_hip_debug.h), through the launch
-// helpers the model runs, on caller-owned buffers.  `status` stands in for the handle's device status word.
-// ---------------------------------------------------------------------------------------------
-static int debug_sizes(const char* who, long B, long n1, long n2, long n3) {
-    if (B <= 0 || n1 <= 0 || n2 <= 0 || n3 <= 0) return fail(PARROT_E_INVALID, std::string(who) + ": non-positive size");
-    if (B > 65535 || n1 > PARROT_DEBUG_MAX_DIM || n2 > PARROT_DEBUG_MAX_DIM || n3 > PARROT_DEBUG_MAX_DIM)
-        return fail(PARROT_E_UNSUPPORTED, std::string(who) + ": B > 65535 or a dimension beyond PARROT_DEBUG_MAX_DIM");
-    return PARROT_OK;
-}
-extern "C" int parrot_debug_durations(const float* ld_raw, const uint8_t* src_valid, const int32_t* src_len, int32_t B, int32_t S, float* log_dur,
-                                      int64_t* dur, int32_t* cum, int32_t* out_len, int32_t* status, void* stream) {
-    if (!ld_raw || !src_valid || !log_dur || !dur || !cum || !out_len || !status) return fail(PARROT_E_INVALID, "debug_durations: null argument");
-    TRY(debug_sizes("debug_durations", B, S, 1, 1));
-    hipStream_t s = (hipStream_t)stream;
-    if (poison_word()) {
-        TRY(poison(log_dur, (size_t)B * S * sizeof(float), s));
-        TRY(poison(dur, (size_t)B * S * sizeof(int64_t), s));
-        TRY(poison(cum, (size_t)B * S * sizeof(int32_t), s));
-        TRY(poison(out_len, (size_t)B * sizeof(int32_t), s));
-    }
-    return launch_durations(ld_raw, src_valid, log_dur, dur, cum, out_len, B, S, src_len, status, s);
-}
-extern "C" int parrot_debug_length_regulate(const float* enc, const int64_t* dur, const int32_t* src_len, const float* pe, int32_t B, int32_t S,
-                                            int32_t D, int32_t L, int32_t P, int32_t row_exact, float* y, uint8_t* tgt_mask, int32_t* cum,
-                                            int32_t* out_len, int32_t* status, void* stream) {
-    if (!enc || !dur || !pe || !y || !cum || !out_len || !status) return fail(PARROT_E_INVALID, "debug_length_regulate: null argument");
-    if (L <= 0) return fail(PARROT_E_INVALID, "debug_length_regulate: L must be > 0");
-    TRY(debug_sizes("debug_length_regulate", B, S, D, L));
-    if (L >= P) return fail(PARROT_E_RANGE, "debug_length_regulate: L >= P (pe[L] out of range, fft.py:18)");
-    hipStream_t s = (hipStream_t)stream;
-    if (poison_word()) {
-        TRY(poison(y, (size_t)B * D * L * sizeof(float), s));
-        TRY(poison(tgt_mask, (size_t)B * L, s));
-        TRY(poison(cum, (size_t)B * S * sizeof(int32_t), s));
-        TRY(poison(out_len, (size_t)B * sizeof(int32_t), s));
-    }
-    TRY(launch_dur_prefix(dur, cum, out_len, B, S, status, src_len, s));
-    return launch_length_regulate(enc, cum, out_len, pe, y, tgt_mask, B, S, L, D, nullptr, 1, row_exact ? 1 : 0, -1, s);
-}
-extern "C" int parrot_debug_argmax_guard(const float* logits, int32_t B, int32_t V, int32_t L, float guard, int32_t row0, const float* x, int32_t D,
-                                         const float* hwt, const float* hb, const float* f, const float* h, const float* w2t, const float* b2,
-                                         int32_t F, const int32_t* gstat_start, int64_t* ids, int32_t* glist, int32_t* gstat, float* gref,
-                                         int32_t* status, void* stream) {
-    if (!logits || !ids || !glist || !gstat || !status) return fail(PARROT_E_INVALID, "debug_argmax_guard: null argument");
-    TRY(debug_sizes("debug_argmax_guard", B, V, L, 1));
-    if (!(guard >= 0.f) || row0 < 0) return fail(PARROT_E_INVALID, "debug_argmax_guard: guard and row0 must be >= 0");
-    const bool on = guard > 0.f, deep = f != nullptr;
-    if (x) {
-        if (!hwt || !gref || (deep && (!h || !w2t))) return fail(PARROT_E_INVALID, "debug_argmax_guard: refinement without hwt / gref (deep form: h, w2t)");
-        TRY(debug_sizes("debug_argmax_guard", B, D, deep ? F : 1, 1));
-        if ((size_t)(D + (deep ? F : 0)) * sizeof(double) > 60000) return fail(PARROT_E_UNSUPPORTED, "debug_argmax_guard: D + F doubles beyond the workgroup's LDS");
-    }
-    if (gstat_start && (gstat_start[0] < 0 || gstat_start[3] < 0 || gstat_start[3] > std::min(gstat_start[0], TIE_GUARD_MAX)))
-        return fail(PARROT_E_INVALID, "debug_argmax_guard: gstat_start needs 0 <= [3] <= min([0], 256)");
-    hipStream_t s = (hipStream_t)stream;
-    if (poison_word()) {  // (a preset list is an input: with gstat_start, and with the guard off, list / statistics / refined rows stay the caller's)
-        TRY(poison(ids, (size_t)B * L * sizeof(int64_t), s));
-        if (on && !gstat_start) {
-            TRY(poison(glist, (size_t)2 * TIE_GUARD_MAX * sizeof(int32_t), s));
-            if (x) TRY(poison(gref, (size_t)TIE_GUARD_MAX * V * sizeof(float), s));
-        }
-    }
-    if (on) {  // what length_regulate_kernel leaves at the start of a decode: a restart, or the caller's second row group of a lane
-        const int32_t restart[4] = {0, 0, 0x7f800000, 0};
-        HIP_TRY(hipMemcpyAsync(gstat, gstat_start ? gstat_start : restart, sizeof(restart), hipMemcpyHostToDevice, s));
-    }
-    RefineArgs r;
-    r.x = x; r.hwt = hwt; r.hb = hb; r.f = f; r.h = h; r.w2t = w2t; r.b2 = b2; r.D = D; r.F = F; r.gref = gref;
-    return launch_argmax_guard(logits, ids, B, V, L, status, guard, on ? glist : nullptr, on ? gstat : nullptr, row0, r, s);
 }
 
 extern "C" int parrot_tte_debug_stages(parrot_tte_t* t, float* const* enc_ptrs, float* const* dec_ptrs) {
@@ -799,11 +480,10 @@ extern "C" int parrot_length_regulator(const float* seq, const int64_t* dur, int
     }
     HIP_TRY(hipMemsetAsync(w.zero, 0, (size_t)D * sizeof(float), s));
     // (B,S,D) -> (B,D,S): the transpose kernel with the roles of C and T swapped
-    hipLaunchKernelGGL(transpose_cf_to_cl_kernel, dim3((D + 63) / 64, (S + 63) / 64, B), dim3(256), 0, s, seq, w.seq_cf, S, D);
-    TRY(launch_dur_prefix(dur, w.cum, w.lens, B, S, nullptr, nullptr, s));
-    TRY(launch_length_regulate(w.seq_cf, w.cum, w.lens, w.zero, w.out_cf, mask, B, S, L, D, nullptr, 1, 0, 0, s));
-    hipLaunchKernelGGL(transpose_cf_to_cl_kernel, dim3((L + 63) / 64, (D + 63) / 64, B), dim3(256), 0, s, w.out_cf, out, D, L);
-    HIP_TRY(hipGetLastError());
+    HIP_TRY(launch_transpose_cf_to_cl(seq, w.seq_cf, B, S, D, s));
+    HIP_TRY(launch_dur_prefix(dur, w.cum, w.lens, B, S, nullptr, nullptr, s));
+    HIP_TRY(launch_length_regulate(w.seq_cf, w.cum, w.lens, w.zero, w.out_cf, mask, B, S, L, D, nullptr, 1, 0, 0, s));
+    HIP_TRY(launch_transpose_cf_to_cl(w.out_cf, out, B, D, L, s));
     HIP_TRY(hipMemcpyAsync(out_lens, w.lens, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
     return PARROT_OK;
 }
@@ -813,40 +493,13 @@ extern "C" int parrot_tte_status_async(parrot_tte_t* t, int32_t* dst_dev, void* 
 // Tie-guard statistics of the last decode, copied to dst_dev[0..2] (device memory) on `stream` without synchronising:
 // {positions whose top-2 logit margin was below the guard, ids changed by the fp64 re-evaluation of the head, the smallest
 // margin of the call as float bits}
-static __global__ void guard_stats_sum_kernel(const int* __restrict__ gstat, int mask, int* __restrict__ dst) {
-    int n = 0, ch = 0, mn = 0x7f800000;
-    for (int l = 0; l < parrot_tte::LANES; ++l)
-        if ((mask >> l) & 1) {
-            n += gstat[4 * l];
-            ch += gstat[4 * l + 1];
-            mn = min(mn, gstat[4 * l + 2]);
-        }
-    dst[0] = n; dst[1] = ch; dst[2] = mn;
-}
-// out row i = the i-th guarded position of the batch, lanes in order (each lane holds at most TIE_GUARD_MAX)
-static __global__ void guard_gather_kernel(const float* __restrict__ gref, const int* __restrict__ glist, const int* __restrict__ gstat, int mask,
-                                           int V, int max_n, float* __restrict__ logits, int* __restrict__ list) {
-    const int i = blockIdx.x;
-    int base = 0, lane = -1, j = 0;
-    for (int l = 0; l < parrot_tte::LANES && lane < 0; ++l)
-        if ((mask >> l) & 1) {
-            const int nl = min(gstat[4 * l], TIE_GUARD_MAX);
-            if (i < base + nl) { lane = l; j = i - base; }
-            base += nl;
-        }
-    if (lane < 0 || i >= max_n) return;
-    const float* src = gref + ((size_t)lane * TIE_GUARD_MAX + j) * V;
-    for (int v = threadIdx.x; v < V; v += blockDim.x) logits[(size_t)i * V + v] = src[v];
-    if (threadIdx.x < 2) list[2 * i + threadIdx.x] = glist[((size_t)lane * TIE_GUARD_MAX + j) * 2 + threadIdx.x];
-}
 extern "C" int parrot_tte_guard_stats_async(parrot_tte_t* t, int32_t* dst_dev, void* stream) {
     if (!t || !dst_dev) return fail(PARROT_E_INVALID, "tte_guard_stats: null argument");
     if (!t->gstat) {
         HIP_TRY(hipMemsetAsync(dst_dev, 0, 3 * sizeof(int), (hipStream_t)stream));
         return PARROT_OK;
     }
-    hipLaunchKernelGGL(guard_stats_sum_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, t->gstat, t->lanes_used, dst_dev);
-    HIP_TRY(hipGetLastError());
+    HIP_TRY(launch_guard_stats_sum(t->gstat, t->lanes_used, dst_dev, (hipStream_t)stream));
     return PARROT_OK;
 }
 // Refined (fp64-evaluated, rounded to fp32) logits of the guarded positions of the last decode: logits_dev (max_n x V floats) and
@@ -854,9 +507,7 @@ extern "C" int parrot_tte_guard_stats_async(parrot_tte_t* t, int32_t* dst_dev, v
 extern "C" int parrot_tte_guard_logits(parrot_tte_t* t, float* logits_dev, int32_t* list_dev, int32_t max_n, void* stream) {
     if (!t || !logits_dev || !list_dev || max_n <= 0) return fail(PARROT_E_INVALID, "tte_guard_logits: null argument");
     if (!t->gref) return fail(PARROT_E_UNSUPPORTED, "tte_guard_logits: the tie guard of this handle is off");
-    hipLaunchKernelGGL(guard_gather_kernel, dim3(max_n), dim3(256), 0, (hipStream_t)stream, t->gref, t->glist, t->gstat, t->lanes_used,
-                       t->cfg.n_codes, max_n, logits_dev, list_dev);
-    HIP_TRY(hipGetLastError());
+    HIP_TRY(launch_guard_gather(t->gref, t->glist, t->gstat, t->lanes_used, t->cfg.n_codes, max_n, logits_dev, list_dev, (hipStream_t)stream));
     return PARROT_OK;
 }
 static int tte_status(int status) { return model_status("tte", status); }

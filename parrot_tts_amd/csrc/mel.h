@@ -2,7 +2,7 @@
 // utils/vocoder/dataset.py:43-69 (reflect pad, framed DFT, magnitude, mel projection, log-clamp) and the L1 distance of two such
 // spectrograms (utils/vocoder/train.py:213).  The two GEMMs -- the framed DFT as a Conv1d over a polyphase view of the padded
 // signal, the mel projection as a 1x1 conv -- are parrot_conv plans (conv_split.h / conv_mfma.h); what is here only moves data.
-// Include it from ONE unit only (the one that launches these), like kernels_misc.h.
+// Include it from ONE unit only (the one that launches these).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

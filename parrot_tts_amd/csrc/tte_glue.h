@@ -1,11 +1,51 @@
-// kernels_misc.h -- the HBM-bound glue kernels of the Parrot-TTS path (gathers, LayerNorm, softmax,
-// duration rounding, length regulator, argmax).  All activations are channel-first (B, C, T).
-// Include it from ONE unit only (the one that launches these): a `static __global__` kernel is emitted by every unit that sees it.
+// tte_glue.h -- the HBM-bound glue kernels of the text-to-unit model (embedding gathers, LayerNorm, duration rounding, length
+// regulator, argmax with the tie guard, a transpose, the tie guard's readers).  All activations are channel-first (B, C, T).
+// The launchers below are defined in tu_tte.hip, which alone sees the kernel bodies (PARROT_TTE_TU).  A launcher carries the
+// launch geometry and nothing else: the callers (host_tte.hip, host_tte_debug.hip) have checked that B fits a grid dimension and
+// that the sizes fit the kernels' int arithmetic.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include "conv_mfma.h"  // (f32x16)
-#include "wave_reduce.h"
+
+namespace parrot {
+
+constexpr int TIE_GUARD_MAX = 256;  // guarded positions per batch (argmax_cf_kernel / tie_guard_refine_kernel below)
+constexpr int ARGMAX_WAVES = 16;    // waves per 64 positions: 62-63 codes each at V = 1000 (sixteen loads in flight per position)
+constexpr int TTE_LANES = 1;        // decoder lanes of a handle (parrot_tte::LANES): one tie-guard list / statistics / refined rows each
+
+// x (B, D, S) <- tok_emb[phones] + pe[S] (row_len: pe[row_len[b]])
+hipError_t launch_tte_embed(const int64_t* phones, const float* emb, const float* pe, const int32_t* row_len, float* x, int B, int S, int D, int vocab,
+                            int* err, hipStream_t s);
+// x (B, C, T) += tab[id[b]]
+hipError_t launch_add_channel_vec(float* x, const int64_t* id, const float* tab, int B, int C, int T, int n_rows, int* err, hipStream_t s);
+// y <- LayerNorm over the channels of x (B, C, T), eps 1e-5, optional ReLU on the input
+hipError_t launch_layernorm(const float* x, const float* g, const float* b, float* y, int B, int C, int T, int relu_in, hipStream_t s);
+// (B, C, T) -> (B, T, C)
+hipError_t launch_transpose_cf_to_cl(const float* x, float* y, int B, int C, int T, hipStream_t s);
+hipError_t launch_durations(const float* ld_raw, const uint8_t* src_valid, float* log_dur, int64_t* dur, int32_t* cum, int32_t* out_len, int B, int S,
+                            const int32_t* src_len, int* err, hipStream_t s);
+hipError_t launch_dur_prefix(const int64_t* dur, int32_t* cum, int32_t* out_len, int B, int S, int* err, const int32_t* src_len, hipStream_t s);
+hipError_t launch_length_regulate(const float* enc, const int32_t* cum, const int32_t* out_len, const float* pe, float* y, uint8_t* tgt_mask, int B,
+                                  int S, int L, int D, int* gstat, int gstat_reset, int row_exact, int pe_stride, hipStream_t s);
+// the tie guard's fp64 re-evaluation (tie_guard_refine_kernel): x == NULL switches it off
+struct RefineArgs {
+    const float *x = nullptr, *hwt = nullptr, *hb = nullptr;                     // (B, D, L), (D, V), (V) nullable
+    const float *f = nullptr, *h = nullptr, *w2t = nullptr, *b2 = nullptr;       // deep form (f != NULL): (B, F, L), (B, D, L), (F, D), (D) nullable
+    int D = 0, F = 0;
+    float* gref = nullptr;
+};
+// argmax + tie guard: gstat = {count, ids changed, min margin (float bits), first list entry of this row group}; glist / gstat NULL: ids only
+hipError_t launch_argmax_guard(const float* logits, int64_t* ids, int B, int V, int L, int* err, float guard, int* glist, int* gstat, int row0,
+                               const RefineArgs& r, hipStream_t s);
+// dst[0..2] <- {count, ids changed, min margin bits} over the lanes of `mask`
+hipError_t launch_guard_stats_sum(const int* gstat, int mask, int* dst, hipStream_t s);
+// logits (max_n, V) / list (max_n, 2) <- the refined rows and (b, t) pairs of the lanes of `mask`, lanes in order
+hipError_t launch_guard_gather(const float* gref, const int* glist, const int* gstat, int mask, int V, int max_n, float* logits, int* list,
+                               hipStream_t s);
+
+}  // namespace parrot
+
+#ifdef PARROT_TTE_TU
 
 namespace parrot {
 
@@ -136,35 +176,6 @@ __global__ __launch_bounds__(NW * 64) void layernorm_cf_kernel(const float* __re
 }
 
 // ---------------------------------------------------------------------------------------------
-// Row softmax of attention scores with a key-padding mask (torch MHA math path, Q3):
-// P[r, :] = softmax(S[r, :] + (-inf where key masked)).  One wave per row, wave-shuffle reductions.
-// rows = B*H*T, row r belongs to batch r / (H*T).  key_valid (B,T) u8 1 = attend.
-// ---------------------------------------------------------------------------------------------
-static __global__ __launch_bounds__(256) void softmax_mask_kernel(float* __restrict__ s, const uint8_t* __restrict__ key_valid, int rows,
-                                                           int T, int HT) {
-    const int lane = threadIdx.x & 63;
-    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= rows) return;
-    const int b = row / HT;
-    float* sr = s + (size_t)row * T;
-    const uint8_t* kv = key_valid + (size_t)b * T;
-    float mx = -INFINITY;
-    for (int t = lane; t < T; t += 64) {
-        const float v = kv[t] ? sr[t] : -INFINITY;
-        mx = fmaxf(mx, v);
-    }
-    mx = wave_max(mx);
-    float sum = 0.f;
-    for (int t = lane; t < T; t += 64) {
-        const float e = kv[t] ? expf(sr[t] - mx) : 0.f;
-        sr[t] = e;
-        sum += e;
-    }
-    sum = wave_sum(sum);
-    for (int t = lane; t < T; t += 64) sr[t] = sr[t] / sum;
-}
-
-// ---------------------------------------------------------------------------------------------
 // Row sums of durations, shared by duration_kernel and dur_prefix_kernel: int64 sums, stored saturated at INT32_MAX (a single
 // duration is capped at INT32_MAX first, so S of them cannot overflow int64).  A row longer than max_len keeps a length the
 // host's checks see: the decode's L < max_len check then fails as pe[L] does in the reference (fft.py:18).
@@ -262,245 +273,6 @@ static __global__ __launch_bounds__(256) void dur_prefix_kernel(const int64_t* _
 }
 
 // ---------------------------------------------------------------------------------------------
-// ModelLoss (modules/loss.py:5-21): CrossEntropyLoss(ignore_index) over (N, V) channel-last fp32 logits + MSELoss of the
-// log-durations over src_mask.  Stage 1: one wave per position -- max-shifted log-sum-exp in fp32, nll = log(sum) - (x[t] - max)
-// (log_softmax's order), and whether the first-max argmax is the target; each block's 16 positions are added in fp64 in row
-// order.  Stage 2 (one block): the block partials and the duration term, each thread a fixed strided slice, then a fixed LDS
-// tree.  No atomics on values: two calls agree bit for bit.  Reads the logits once (V <= 1024 and 16-byte rows: from registers).
-// The gradient (train.py:72-85, loss.backward()): loss_count_kernel counts the valid targets and the set mask bytes first (the
-// scales w_code / n_valid and 2 w_dur / n_src must be known before a scaled element can be written) and writes the duration
-// gradient; loss_rows_kernel<true> is stage 1 with one more step per row, g_code (softmax - onehot) from the registers that hold
-// the row (an ignored row: zeros, a bad target: NaN); stage 2 is unchanged.  Every output element is written exactly once.
-// ---------------------------------------------------------------------------------------------
-constexpr int LOSS_WAVES = 16;      // positions per stage-1 block
-constexpr int LOSS_CHUNKS = 4;      // float4 per lane held in registers: V <= 1024 on the vector path
-constexpr int LOSS_REDUCE = 1024;   // stage-2 threads (and loss_count_kernel's)
-struct LossCounts { int32_t n_valid, n_correct, n_bad, first_bad_row; };
-struct LossScale { float g_code, g_dur; int32_t n_valid, n_src; };  // g_code = w_code / n_valid, g_dur = 2 w_dur / n_src: fp64, rounded once
-
-// weights (nullable: {1, 1}) = {w_code, w_dur} fp64; grad_log_dur (nullable) (n_src) <- g_dur (log_dur - log(dur + 1)) under the mask, 0 elsewhere
-static __global__ __launch_bounds__(LOSS_REDUCE) void loss_count_kernel(const int64_t* __restrict__ tgt, int N, int V, int64_t ignore,
-                                                                        const float* __restrict__ log_dur, const int64_t* __restrict__ dur,
-                                                                        const uint8_t* __restrict__ src_mask, int n_src,
-                                                                        const double* __restrict__ weights, LossScale* __restrict__ scale,
-                                                                        float* __restrict__ grad_log_dur) {
-    __shared__ int s_valid[LOSS_REDUCE], s_src[LOSS_REDUCE];
-    const int tid = threadIdx.x;
-    int nv = 0, ns = 0;
-    for (int i = tid; i < N; i += LOSS_REDUCE) {
-        const int64_t t = tgt[i];
-        nv += t != ignore && t >= 0 && t < V;  // loss_rows_kernel's states 1 and 2
-    }
-    for (int i = tid; i < n_src; i += LOSS_REDUCE) ns += src_mask[i] != 0;
-    s_valid[tid] = nv; s_src[tid] = ns;
-    __syncthreads();
-    for (int h = LOSS_REDUCE / 2; h > 0; h >>= 1) {
-        if (tid < h) {
-            s_valid[tid] += s_valid[tid + h];
-            s_src[tid] += s_src[tid + h];
-        }
-        __syncthreads();
-    }
-    nv = s_valid[0]; ns = s_src[0];
-    const double w_code = weights ? weights[0] : 1.0, w_dur = weights ? weights[1] : 1.0;
-    // (nothing valid: the quotient is inf or NaN and multiplies nothing -- every row is ignored, every mask byte clear)
-    const float g_code = (float)(w_code / (double)nv), g_dur = (float)(2.0 * w_dur / (double)ns);
-    if (tid == 0) *scale = LossScale{g_code, g_dur, nv, ns};
-    if (grad_log_dur)
-        for (int i = tid; i < n_src; i += LOSS_REDUCE)
-            grad_log_dur[i] = src_mask[i] ? g_dur * (log_dur[i] - logf((float)dur[i] + 1.0f)) : 0.f;  // the forward's difference
-}
-
-// GRAD: also grad (N, V) <- scale->g_code (softmax(x) - onehot(target)) per valid row, 0 for an ignored one, NaN for a bad target
-template <bool GRAD>
-static __global__ __launch_bounds__(64 * LOSS_WAVES) void loss_rows_kernel(const float* __restrict__ logits, const int64_t* __restrict__ tgt,
-                                                                         int N, int V, int64_t ignore, double* __restrict__ part_nll,
-                                                                         LossCounts* __restrict__ part_cnt, int64_t* __restrict__ part_bad,
-                                                                         const LossScale* __restrict__ scale, float* __restrict__ grad) {
-    __shared__ double s_nll[LOSS_WAVES];
-    __shared__ int s_st[LOSS_WAVES];  // 0 skipped, 1 valid, 2 valid and argmax == target, 3 target out of range
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int row = blockIdx.x * LOSS_WAVES + wave;  // wave-uniform: every branch below is uniform
-    int st = 0;
-    double nll = 0.0;
-    if (row < N) {
-        const float* __restrict__ x = logits + (size_t)row * V;
-        const bool vec = (V & 3) == 0 && V <= 256 * LOSS_CHUNKS && ((uintptr_t)logits & 15) == 0;
-        // (vector path: the row's loads are issued together with the target's, not behind it -- an ignored row reads its logits too)
-        float4 r[LOSS_CHUNKS];
-        if (vec) {
-#pragma unroll
-            for (int k = 0; k < LOSS_CHUNKS; ++k) {
-                const int i = (k * 64 + lane) * 4;
-                r[k] = i < V ? *reinterpret_cast<const float4*>(x + i) : make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
-            }
-        }
-        const int64_t tg = tgt[row];
-        float* __restrict__ g = GRAD ? grad + (size_t)row * V : nullptr;
-        const bool gvec = ((uintptr_t)grad & 15) == 0;  // (V % 4 == 0 on the vector path: every row of an aligned base is aligned)
-        auto put4 = [&](int i, float a, float b, float c, float d) {
-            if (gvec) {
-                *reinterpret_cast<float4*>(g + i) = make_float4(a, b, c, d);
-            } else {
-                g[i] = a; g[i + 1] = b; g[i + 2] = c; g[i + 3] = d;
-            }
-        };
-        if (tg == ignore || tg < 0 || tg >= V) {
-            st = tg == ignore ? 0 : 3;
-            if constexpr (GRAD) {  // an ignored row is 0 throughout; nothing is indexed through a bad target: its row is NaN
-                const float fill = st == 0 ? 0.f : NAN;
-                if (vec) {
-#pragma unroll
-                    for (int k = 0; k < LOSS_CHUNKS; ++k) {
-                        const int i = (k * 64 + lane) * 4;
-                        if (i < V) put4(i, fill, fill, fill, fill);
-                    }
-                } else {
-                    for (int i = lane; i < V; i += 64) g[i] = fill;
-                }
-            }
-        } else {
-            const float xt = x[tg];
-            float m = -INFINITY, s = 0.f;
-            int mi = V;
-            if (vec) {
-#pragma unroll
-                for (int k = 0; k < LOSS_CHUNKS; ++k) {
-                    const int i = (k * 64 + lane) * 4;
-                    const float e[4] = {r[k].x, r[k].y, r[k].z, r[k].w};
-#pragma unroll
-                    for (int j = 0; j < 4; ++j)
-                        if (i + j < V && e[j] > m) { m = e[j]; mi = i + j; }
-                }
-                for (int o = 32; o > 0; o >>= 1) {  // (value, index): larger value, then smaller index -- torch.argmax's first maximum
-                    const float om = __shfl_xor(m, o);
-                    const int oi = __shfl_xor(mi, o);
-                    if (om > m || (om == m && oi < mi)) { m = om; mi = oi; }
-                }
-#pragma unroll
-                for (int k = 0; k < LOSS_CHUNKS; ++k) {
-                    const int i = (k * 64 + lane) * 4;
-                    const float e[4] = {r[k].x, r[k].y, r[k].z, r[k].w};
-#pragma unroll
-                    for (int j = 0; j < 4; ++j)
-                        if (i + j < V) s += expf(e[j] - m);
-                }
-            } else {  // any V / alignment: two passes over the row (the second from cache)
-                for (int i = lane; i < V; i += 64)
-                    if (x[i] > m) { m = x[i]; mi = i; }
-                for (int o = 32; o > 0; o >>= 1) {
-                    const float om = __shfl_xor(m, o);
-                    const int oi = __shfl_xor(mi, o);
-                    if (om > m || (om == m && oi < mi)) { m = om; mi = oi; }
-                }
-                for (int i = lane; i < V; i += 64) s += expf(x[i] - m);
-            }
-            s = wave_sum(s);
-            nll = (double)(logf(s) - (xt - m));
-            st = mi == (int)tg ? 2 : 1;
-            if constexpr (GRAD) {
-                const float gc = scale->g_code, inv = 1.0f / s;
-                const int t = (int)tg;
-                if (vec) {  // from the registers that hold the row
-#pragma unroll
-                    for (int k = 0; k < LOSS_CHUNKS; ++k) {
-                        const int i = (k * 64 + lane) * 4;
-                        if (i < V)
-                            put4(i, gc * (expf(r[k].x - m) * inv - (i == t ? 1.f : 0.f)), gc * (expf(r[k].y - m) * inv - (i + 1 == t ? 1.f : 0.f)),
-                                 gc * (expf(r[k].z - m) * inv - (i + 2 == t ? 1.f : 0.f)), gc * (expf(r[k].w - m) * inv - (i + 3 == t ? 1.f : 0.f)));
-                    }
-                } else {  // a third pass, from cache
-                    for (int i = lane; i < V; i += 64) g[i] = gc * (expf(x[i] - m) * inv - (i == t ? 1.f : 0.f));
-                }
-            }
-        }
-    }
-    if (lane == 0) {
-        s_nll[wave] = nll;
-        s_st[wave] = st;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double a = 0.0;
-        LossCounts c{0, 0, 0, -1};
-        int64_t bad_t = 0;
-        for (int w = 0; w < LOSS_WAVES; ++w) {
-            a += s_nll[w];
-            c.n_valid += s_st[w] == 1 || s_st[w] == 2;
-            c.n_correct += s_st[w] == 2;
-            if (s_st[w] == 3 && c.n_bad++ == 0) {
-                c.first_bad_row = blockIdx.x * LOSS_WAVES + w;
-                bad_t = tgt[c.first_bad_row];
-            }
-        }
-        part_nll[blockIdx.x] = a;
-        part_cnt[blockIdx.x] = c;
-        part_bad[blockIdx.x] = bad_t;
-    }
-}
-
-// out[0..7] = {sum nll, n_valid, n_correct, sum sq, n_src, n_bad, first bad target, 0}; losses (nullable) = {total, code, dur} fp32
-static __global__ __launch_bounds__(LOSS_REDUCE) void loss_reduce_kernel(const double* __restrict__ part_nll, const LossCounts* __restrict__ part_cnt,
-                                                                         const int64_t* __restrict__ part_bad, int nblk,
-                                                                         const float* __restrict__ log_dur, const int64_t* __restrict__ dur,
-                                                                         const uint8_t* __restrict__ src_mask, int n_src, double* __restrict__ out,
-                                                                         float* __restrict__ losses) {
-    __shared__ double s_nll[LOSS_REDUCE], s_sq[LOSS_REDUCE];
-    __shared__ int s_valid[LOSS_REDUCE], s_correct[LOSS_REDUCE], s_bad[LOSS_REDUCE], s_src[LOSS_REDUCE];
-    __shared__ int s_first[LOSS_REDUCE];  // lowest-numbered block with an out-of-range target (nblk: none)
-    const int tid = threadIdx.x;
-    double a = 0.0, q = 0.0;
-    int nv = 0, nc = 0, nb = 0, ns = 0, first = nblk;
-    for (int i = tid; i < nblk; i += LOSS_REDUCE) {
-        const LossCounts c = part_cnt[i];
-        a += part_nll[i];
-        nv += c.n_valid;
-        nc += c.n_correct;
-        nb += c.n_bad;
-        if (c.n_bad && i < first) first = i;
-    }
-    for (int i = tid; i < n_src; i += LOSS_REDUCE) {
-        if (!src_mask[i]) continue;
-        const float d = log_dur[i] - logf((float)dur[i] + 1.0f);  // log(duration.float() + 1), loss.py:14
-        q += (double)(d * d);
-        ++ns;
-    }
-    s_nll[tid] = a; s_sq[tid] = q; s_valid[tid] = nv; s_correct[tid] = nc; s_bad[tid] = nb; s_src[tid] = ns; s_first[tid] = first;
-    __syncthreads();
-    for (int h = LOSS_REDUCE / 2; h > 0; h >>= 1) {
-        if (tid < h) {
-            s_nll[tid] += s_nll[tid + h];
-            s_sq[tid] += s_sq[tid + h];
-            s_valid[tid] += s_valid[tid + h];
-            s_correct[tid] += s_correct[tid + h];
-            s_bad[tid] += s_bad[tid + h];
-            s_src[tid] += s_src[tid + h];
-            s_first[tid] = min(s_first[tid], s_first[tid + h]);
-        }
-        __syncthreads();
-    }
-    if (tid == 0) {
-        out[0] = s_nll[0];
-        out[1] = (double)s_valid[0];
-        out[2] = (double)s_correct[0];
-        out[3] = s_sq[0];
-        out[4] = (double)s_src[0];
-        out[5] = (double)s_bad[0];
-        out[6] = s_first[0] < nblk ? (double)part_bad[s_first[0]] : 0.0;
-        out[7] = 0.0;
-        if (losses) {
-            const float code = (float)(s_nll[0] / (double)s_valid[0]);  // 0 / 0 = NaN: an all-ignored batch, as torch gives
-            const float durl = (float)(s_sq[0] / (double)s_src[0]);
-            losses[0] = code + durl;  // loss.py:19, in fp32
-            losses[1] = code;
-            losses[2] = durl;
-        }
-    }
-}
-
-constexpr int TIE_GUARD_MAX = 256;  // guarded positions per batch (argmax_cf_kernel / tie_guard_refine_kernel below)
-
-// ---------------------------------------------------------------------------------------------
 // Length regulator + positional row (duration.py:6-24, parrot.py:106, data.py:8-20):
 // y[b, c, t] = (t < len_b ? enc[b, c, src(t)] : 0) + pe[L][c], src(t) = first s with cum[b,s] > t;
 // tgt_mask[b,t] = t <= len_b (Q2).   grid (ceil(L/64), B).  idx is recomputed per (b,t) once and
@@ -551,7 +323,6 @@ static __global__ __launch_bounds__(256) void length_regulate_kernel(const float
 // margin; positions whose margin is below `guard` are appended to `glist` ((b, t) pairs, at most TIE_GUARD_MAX) and counted in
 // gstat[0], the smallest margin of the call lands in gstat[2] (float bits; positive floats order like ints) --
 // tie_guard_refine_kernel then re-evaluates the head for exactly those positions in fp64.
-constexpr int ARGMAX_WAVES = 16;  // waves per 64 positions: 62-63 codes each at V = 1000 (sixteen loads in flight per position)
 static __global__ __launch_bounds__(64 * ARGMAX_WAVES) void argmax_cf_kernel(const float* __restrict__ logits, int64_t* __restrict__ ids, int V, int L,
                                                                int* __restrict__ err, float guard, int* __restrict__ glist,
                                                                int* __restrict__ gstat, int row0 = 0) {
@@ -706,66 +477,35 @@ static __global__ __launch_bounds__(256) void transpose_cf_to_cl_kernel(const fl
     }
 }
 
-
-// the batched fp32 MFMA GEMM of the three-kernel attention path (operand addressing: attn.h)
-struct BgemmParams {
-    const float* A;
-    const float* B;
-    float* C;
-    int M, N, K;
-    long a_sk, a_sm, b_sk, b_sn;      // element strides
-    long a_zb, a_zh, b_zb, b_zh;      // batch / head offsets
-    long c_zb, c_zh, ldc;
-    int H;
-    float alpha;
-};
-
-static __global__ __launch_bounds__(256) void bgemm_mfma_kernel(const BgemmParams p) {
-    constexpr int KC = 32, RS = 65;
-    __shared__ float As[KC][RS];
-    __shared__ float Bs[KC][RS];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wm = wave >> 1, wn = wave & 1, half = lane >> 5, l31 = lane & 31;
-    const int z = blockIdx.z, zb = z / p.H, zh = z - zb * p.H;
-    const int m0 = blockIdx.y * 64, n0 = blockIdx.x * 64;
-    const float* __restrict__ A = p.A + zb * p.a_zb + zh * p.a_zh;
-    const float* __restrict__ B = p.B + zb * p.b_zb + zh * p.b_zh;
-    f32x16 acc;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-
-    const bool a_kfast = (p.a_sk == 1), b_kfast = (p.b_sk == 1);
-    for (int k0 = 0; k0 < p.K; k0 += KC) {
-#pragma unroll
-        for (int i = 0; i < (KC * 64) / 256; ++i) {
-            const int idx = i * 256 + tid;
-            int kk, mm;
-            if (a_kfast) { mm = idx / KC; kk = idx % KC; } else { kk = idx / 64; mm = idx % 64; }
-            float v = 0.f;
-            if (k0 + kk < p.K && m0 + mm < p.M) v = A[(long)(k0 + kk) * p.a_sk + (long)(m0 + mm) * p.a_sm] * p.alpha;
-            As[kk][mm] = v;
-            int kb, nn;
-            if (b_kfast) { nn = idx / KC; kb = idx % KC; } else { kb = idx / 64; nn = idx % 64; }
-            float w = 0.f;
-            if (k0 + kb < p.K && n0 + nn < p.N) w = B[(long)(k0 + kb) * p.b_sk + (long)(n0 + nn) * p.b_sn];
-            Bs[kb][nn] = w;
+// Tie-guard statistics of the last decode over the lanes of `mask`: dst[0..2] = {positions whose top-2 logit margin was below the
+// guard, ids changed by the fp64 re-evaluation of the head, the smallest margin of the call as float bits}
+static __global__ void guard_stats_sum_kernel(const int* __restrict__ gstat, int mask, int* __restrict__ dst) {
+    int n = 0, ch = 0, mn = 0x7f800000;
+    for (int l = 0; l < TTE_LANES; ++l)
+        if ((mask >> l) & 1) {
+            n += gstat[4 * l];
+            ch += gstat[4 * l + 1];
+            mn = min(mn, gstat[4 * l + 2]);
         }
-        __syncthreads();
-#pragma unroll
-        for (int ks = 0; ks < KC; ks += 2) {
-            const float a = As[ks + half][wm * 32 + l31];
-            const float b = Bs[ks + half][wn * 32 + l31];
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, acc, 0, 0, 0);
+    dst[0] = n; dst[1] = ch; dst[2] = mn;
+}
+// out row i = the i-th guarded position of the batch, lanes in order (each lane holds at most TIE_GUARD_MAX)
+static __global__ void guard_gather_kernel(const float* __restrict__ gref, const int* __restrict__ glist, const int* __restrict__ gstat, int mask,
+                                           int V, int max_n, float* __restrict__ logits, int* __restrict__ list) {
+    const int i = blockIdx.x;
+    int base = 0, lane = -1, j = 0;
+    for (int l = 0; l < TTE_LANES && lane < 0; ++l)
+        if ((mask >> l) & 1) {
+            const int nl = min(gstat[4 * l], TIE_GUARD_MAX);
+            if (i < base + nl) { lane = l; j = i - base; }
+            base += nl;
         }
-        __syncthreads();
-    }
-    float* __restrict__ C = p.C + zb * p.c_zb + zh * p.c_zh;
-    const int n = n0 + wn * 32 + l31;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const int m = m0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
-        if (m < p.M && n < p.N) C[(long)m * p.ldc + n] = acc[r];
-    }
+    if (lane < 0 || i >= max_n) return;
+    const float* src = gref + ((size_t)lane * TIE_GUARD_MAX + j) * V;
+    for (int v = threadIdx.x; v < V; v += blockDim.x) logits[(size_t)i * V + v] = src[v];
+    if (threadIdx.x < 2) list[2 * i + threadIdx.x] = glist[((size_t)lane * TIE_GUARD_MAX + j) * 2 + threadIdx.x];
 }
 
 }  // namespace parrot
+
+#endif  // PARROT_TTE_TU

@@ -1,5 +1,6 @@
-// tu_attn.hip -- one translation unit of libparrot_hip.so (parrot_tts_amd/build.py compiles them in parallel): the kernel
-// instantiations behind the entry points below.
+// tu_attn.hip -- one translation unit of libparrot_hip.so (parrot_tts_amd/build.py compiles them in parallel): the flash attention
+// kernel instantiations behind the entry point below (the fp32-MFMA attention cores are tu_tte.hip's).
+#define PARROT_ATTN_FLASH_TU
 #include "attn.h"
 namespace parrot {
 hipError_t launch_attn_flash(const AttnParams& p, int B, hipStream_t s) {

@@ -211,7 +211,7 @@ def debug_layernorm(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, re
     return out
 
 
-TIE_GUARD_MAX = 256  # guarded positions per decoder lane (csrc/kernels_misc.h)
+TIE_GUARD_MAX = 256  # guarded positions per decoder lane (csrc/tte_glue.h)
 
 
 def _dev_arg(t: Optional[torch.Tensor], dtype, shape, dev, name: str) -> None:

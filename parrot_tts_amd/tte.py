@@ -131,7 +131,7 @@ class Parrot(RangeFallbackModule):
     # ---- forward ------------------------------------------------------------------------------
     @staticmethod
     def _raise_status(code: int, who: str):
-        """Device status codes (csrc/kernels_misc.h) -> the exceptions the reference raises / this package promises."""
+        """Device status codes (csrc/tte_glue.h) -> the exceptions the reference raises / this package promises."""
         if code == 0:
             return
         if code == 6:  # parrot_tte_set_durations: torch.repeat_interleave's error (duration.py:14)

@@ -1,5 +1,5 @@
-"""GPU: the TTE's three attention cores and its LayerNorm on their own (parrot_debug_attention / parrot_debug_layernorm: the launch
-code of the FFT block itself, csrc/host_tte.hip attention_core() / layernorm()), element-wise against fp64.
+"""GPU: the TTE's three attention cores and its LayerNorm on their own (parrot_debug_attention / parrot_debug_layernorm: the
+launchers the FFT block itself calls, csrc/attn.h launch_attention_core() / csrc/tte_glue.h launch_layernorm()), element-wise against fp64.
 
 Attention.  The yardstick is the torch MHA math path in plain torch on the CPU in fp64, on the channel-first (B, 3, D, T) layout:
 q * sqrt(1 / hd), q k^T, masked_fill(-inf) over the masked keys, softmax, . v.  The same formula in fp32 on the CPU gives e32.

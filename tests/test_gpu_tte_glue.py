@@ -1,5 +1,5 @@
 """GPU: the TTE's integer and gather kernels on their own (parrot_debug_durations / parrot_debug_length_regulate /
-parrot_debug_argmax_guard: the launch helpers of csrc/host_tte.hip that the model itself calls; the embedding kernels through the
+parrot_debug_argmax_guard: the launchers of csrc/tte_glue.h that the model itself calls; the embedding kernels through the
 parrot_tte_debug_stages taps), each against the plain numpy restatement of tests/tte_glue_ref.py, which tests/test_tte_glue_cpu.py
 pins against torch and the oracle.
 

@@ -1,4 +1,4 @@
-"""Plain numpy restatements of the TTE's glue kernels (csrc/kernels_misc.h: duration_kernel, dur_prefix_kernel,
+"""Plain numpy restatements of the TTE's glue kernels (csrc/tte_glue.h: duration_kernel, dur_prefix_kernel,
 length_regulate_kernel, argmax_cf_kernel, tie_guard_refine_kernel), pinned on the CPU by tests/test_tte_glue_cpu.py against torch
 and the oracle, and held against the device by tests/test_gpu_tte_glue.py.  Nothing here imports the library."""
 import numpy as np
