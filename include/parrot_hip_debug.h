@@ -151,6 +151,21 @@ size_t parrot_debug_colsum_workspace_bytes(int32_t R, int32_t M);
 int parrot_debug_colsum(const parrot_debug_colsum_desc* d, void* ws, size_t ws_bytes, void* stream);
 int parrot_debug_bn_train(const parrot_debug_bn_train_desc* d, void* stream);
 int parrot_debug_bn_relu_bwd(const parrot_debug_bn_bwd_desc* d, void* stream);
+/* Tests: the aligner's bidirectional LSTM recurrence on its own, through the step loop parrot_aligner_forward runs (kernel 0:
+ * lstm_step_kernel, csrc/aligner.h) or the one parrot_aligner_train_forward runs (kernel 1: lstm_train_step_kernel,
+ * csrc/aligner_train.h), on caller-owned DEVICE buffers.  w_hh [2][4H][H] (forward, backward direction; gates i, f, g, o), xproj
+ * (B, T, 8H) = W_ih x + b_ih + b_hh of both directions, h0 / c0 [2][B][H] the state before step 0 (both NULL: zeros).  Steps
+ * 0 .. n_steps - 1 only: the forward direction writes frames 0 .. n_steps - 1 of out (B, T, 2H) [forward, backward], the backward
+ * direction frames T - 1 .. T - n_steps; every other element of out (and of gates / c_all) is left as the caller gave it.  h_n / c_n
+ * [2][B][H]: the state after the last step.  gates (B, T, 8H): sigmoid(i), sigmoid(f), tanh(g), sigmoid(o) per direction, and c_all
+ * (B, T, 2H): kernel 1 only (kernel 0: both NULL).  ws: parrot_debug_lstm_workspace_bytes (0 for sizes that are not valid).
+ * Before any launch: a null argument, h0 without c0, B, T or H < 1, n_steps outside [1, T], a kernel other than 0 / 1, gates / c_all
+ * that do not match the kernel: PARROT_E_INVALID; H not a multiple of 16 or > 1024, B > 65535, T > 32768, a workspace that is too
+ * small: PARROT_E_UNSUPPORTED. */
+size_t parrot_debug_lstm_workspace_bytes(int32_t B, int32_t T, int32_t H, int32_t kernel);
+int parrot_debug_lstm(const float* w_hh, const float* xproj, const float* h0, const float* c0, int32_t B, int32_t T, int32_t H,
+                      int32_t n_steps, int32_t kernel, float* out, float* h_n, float* c_n, float* gates, float* c_all, void* ws,
+                      size_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }

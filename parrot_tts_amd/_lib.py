@@ -233,6 +233,8 @@ SIGNATURES = {
     "parrot_debug_colsum": (C.c_int, [C.POINTER(DebugColsumDesc), vp, sz, vp]),
     "parrot_debug_bn_train": (C.c_int, [C.POINTER(DebugBnTrainDesc), vp]),
     "parrot_debug_bn_relu_bwd": (C.c_int, [C.POINTER(DebugBnBwdDesc), vp]),
+    "parrot_debug_lstm_workspace_bytes": (sz, [i32, i32, i32, i32]),
+    "parrot_debug_lstm": (C.c_int, [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, sz, vp]),
     "parrot_gan_loss_tile": (i32, []),
     "parrot_gan_loss_workspace_bytes": (sz, [C.POINTER(GanTerm), i32]),
     "parrot_gan_loss": (C.c_int, [C.POINTER(GanTerm), i32, vp, C.c_double, vp, vp, vp, sz, vp]),

@@ -30,6 +30,9 @@ struct LstmStepParams {
 };
 
 hipError_t launch_lstm_step(const LstmStepParams& p, hipStream_t s);
+// steps 0 .. n_steps - 1 of the recurrence from (h0, c0) [2][B][H] (null: zeros) through hbuf [2][2][B][H] and q.c: the loop of
+// parrot_aligner_forward (host_aligner.hip).  A PARROT_* code.
+int lstm_run_steps(LstmStepParams q, float* hbuf, const float* h0, const float* c0, int n_steps, hipStream_t s);
 // in (B, R, C) -> out (B, C, R)
 hipError_t launch_align_transpose(const float* in, float* out, int B, int R, int C, hipStream_t s);
 // out[b][c][t] = affine_c(relu?(sum_g in[b][g Mg + c][t])), in (B, G Mg, T), out (B, C, T) (may alias `in` when G == 1, Mg == C)
@@ -100,7 +103,11 @@ __global__ __launch_bounds__(256) void lstm_step_kernel(const LstmStepParams p) 
                 const float go = xp[3 * H] + gates[(3 * LSTM_UNITS + uu) * LSTM_BT + bb];
                 const float i_ = 1.f / (1.f + expf(-gi)), f_ = 1.f / (1.f + expf(-gf)), g_ = tanhf(gg), o_ = 1.f / (1.f + expf(-go));
                 const size_t ci = ((size_t)dir * B + b) * H + unit;
-                const float cn = __fadd_rn(__fmul_rn(f_, p.c[ci]), __fmul_rn(i_, g_));
+                // c = fma(f, c, fl32(i g)): two roundings, spelled out, here and in lstm_train_step_kernel alike.  (It used to read
+                // __fadd_rn(__fmul_rn(f, c), __fmul_rn(i, g)); HIP's _rn intrinsics are a plain `*` and `+` under the default
+                // -ffp-contract=fast, and the compiler fused one product into the add: f c here -- this very FMA -- but i g in the
+                // training kernel, so the two kernels differed in the last bit of c.)
+                const float cn = fmaf(f_, p.c[ci], i_ * g_);
                 const float hn = o_ * tanhf(cn);
                 p.c[ci] = cn;
                 p.h_next[ci] = hn;

@@ -432,7 +432,7 @@ __global__ __launch_bounds__(256) void lstm_train_step_kernel(const LstmTrainPar
                 const float go = xp[3 * H] + gates[(3 * AT_UNITS + uu) * AT_BT + bb];
                 const float i_ = 1.f / (1.f + expf(-gi)), f_ = 1.f / (1.f + expf(-gf)), g_ = tanhf(gg), o_ = 1.f / (1.f + expf(-go));
                 const size_t ci = ((size_t)dir * B + b) * H + unit;
-                const float cn = __fadd_rn(__fmul_rn(f_, p.c[ci]), __fmul_rn(i_, g_));
+                const float cn = fmaf(f_, p.c[ci], i_ * g_);  // (lstm_step_kernel's own FMA: see the note there)
                 const float hn = o_ * tanhf(cn);
                 p.c[ci] = cn;
                 p.h_next[ci] = hn;

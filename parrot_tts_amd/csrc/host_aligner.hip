@@ -155,6 +155,23 @@ static int align_run_plan(const AlignPlan& p, const float* x, float* part, float
     HIP_TRY(launch_align_epilogue(part, y, p.scale, p.shift, B, p.C, T, p.G, p.Mg, p.relu, s));
     return PARROT_OK;
 }
+// The recurrence as the forward runs it: the initial state into half 0 of the h double buffer hbuf [2][2][B][H] and into q.c (zeros
+// when h0 / c0 are null, else device copies), then one launch per step, each reading the half the step before wrote.  Afterwards h
+// of the last step is half n_steps & 1 of hbuf and c is q.c.  Also behind parrot_debug_lstm (host_aligner_train.hip).
+int parrot::lstm_run_steps(LstmStepParams q, float* hbuf, const float* h0, const float* c0, int n_steps, hipStream_t s) {
+    const size_t hn = (size_t)2 * q.B * q.H;
+    if (h0) HIP_TRY(hipMemcpyAsync(hbuf, h0, hn * sizeof(float), hipMemcpyDeviceToDevice, s));
+    else HIP_TRY(hipMemsetAsync(hbuf, 0, hn * sizeof(float), s));
+    if (c0) HIP_TRY(hipMemcpyAsync(q.c, c0, hn * sizeof(float), hipMemcpyDeviceToDevice, s));
+    else HIP_TRY(hipMemsetAsync(q.c, 0, hn * sizeof(float), s));
+    for (int step = 0; step < n_steps; ++step) {
+        q.step = step;
+        q.h_prev = hbuf + (size_t)(step & 1) * hn;
+        q.h_next = hbuf + (size_t)((step + 1) & 1) * hn;
+        HIP_TRY(launch_lstm_step(q, s));
+    }
+    return PARROT_OK;
+}
 extern "C" int parrot_aligner_forward(parrot_aligner_t* al, const float* mel, int32_t B, int32_t T, float* logits, void* ws, size_t ws_bytes,
                                       void* stream) {
     if (!al || !mel || !logits || !ws) return fail(PARROT_E_INVALID, "aligner_forward: null argument");
@@ -176,18 +193,10 @@ extern "C" int parrot_aligner_forward(parrot_aligner_t* al, const float* mel, in
     if (al->dbg_bn3) HIP_TRY(hipMemcpyAsync(al->dbg_bn3, w.a, (size_t)B * D * T * sizeof(float), hipMemcpyDeviceToDevice, s));
     TRY(align_run_plan(al->plan[3], w.a, w.part, w.xp_cf, B, T, s));
     HIP_TRY(launch_align_transpose(w.xp_cf, w.xp, B, 8 * H, T, s));
-    const size_t hn = (size_t)2 * B * H;
-    HIP_TRY(hipMemsetAsync(w.h, 0, hn * sizeof(float), s));  // h_0 = c_0 = 0 (nn.LSTM without an initial state)
-    HIP_TRY(hipMemsetAsync(w.c, 0, hn * sizeof(float), s));
     LstmStepParams q{};
     q.w_hh = al->w_hh; q.xproj = w.xp; q.c = w.c; q.out = w.lstm;
     q.B = B; q.T = T; q.H = H;
-    for (int step = 0; step < T; ++step) {
-        q.step = step;
-        q.h_prev = w.h + (size_t)(step & 1) * hn;
-        q.h_next = w.h + (size_t)((step + 1) & 1) * hn;
-        HIP_TRY(launch_lstm_step(q, s));
-    }
+    TRY(lstm_run_steps(q, w.h, nullptr, nullptr, T, s));  // h_0 = c_0 = 0 (nn.LSTM without an initial state)
     if (al->dbg_lstm) HIP_TRY(hipMemcpyAsync(al->dbg_lstm, w.lstm, (size_t)B * T * 2 * H * sizeof(float), hipMemcpyDeviceToDevice, s));
     HIP_TRY(launch_align_transpose(w.lstm, w.lstm_cf, B, T, 2 * H, s));
     TRY(align_run_plan(al->plan[4], w.lstm_cf, w.part, w.logits_cf, B, T, s));

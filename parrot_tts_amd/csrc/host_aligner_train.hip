@@ -112,6 +112,23 @@ int wgrad(WgradParams q, float* part, float* out, long o_sm, long o_sk, long o_s
     HIP_TRY(launch_wgrad_reduce(part, wgrad_chunks(q.R), q.ntaps, q.M, q.K, out, o_sm, o_sk, o_sj, s));
     return PARROT_OK;
 }
+// The training recurrence as the forward runs it: lstm_run_steps (host_aligner.hip) over lstm_train_step_kernel.  The initial state
+// into half 0 of hbuf [2][2][B][H] and into q.c (zeros when h0 / c0 are null), one launch per step; afterwards h of the last step is
+// half n_steps & 1 of hbuf and c is q.c.  Also behind parrot_debug_lstm.
+int lstm_train_run_steps(LstmTrainParams q, float* hbuf, const float* h0, const float* c0, int n_steps, hipStream_t s) {
+    const size_t hn = (size_t)2 * q.B * q.H;
+    if (h0) HIP_TRY(hipMemcpyAsync(hbuf, h0, hn * sizeof(float), hipMemcpyDeviceToDevice, s));
+    else HIP_TRY(hipMemsetAsync(hbuf, 0, hn * sizeof(float), s));
+    if (c0) HIP_TRY(hipMemcpyAsync(q.c, c0, hn * sizeof(float), hipMemcpyDeviceToDevice, s));
+    else HIP_TRY(hipMemsetAsync(q.c, 0, hn * sizeof(float), s));
+    for (int step = 0; step < n_steps; ++step) {
+        q.step = step;
+        q.h_prev = hbuf + (size_t)(step & 1) * hn;
+        q.h_next = hbuf + (size_t)((step + 1) & 1) * hn;
+        HIP_TRY(launch_lstm_train_step(q, s));
+    }
+    return PARROT_OK;
+}
 
 }  // namespace
 
@@ -177,19 +194,11 @@ extern "C" int parrot_aligner_train_forward(const parrot_aligner_cfg* cfg, const
         g.bias1 = wt->b_hh[d];
         HIP_TRY(launch_tap_gemm(g, B, s));
     }
-    const size_t hn = (size_t)2 * B * H;
-    HIP_TRY(hipMemsetAsync(w.hbuf, 0, hn * sizeof(float), s));  // h_0 = c_0 = 0
-    HIP_TRY(hipMemsetAsync(w.cbuf, 0, hn * sizeof(float), s));
     LstmTrainParams q{};
     q.w_hh[0] = wt->w_hh[0]; q.w_hh[1] = wt->w_hh[1];
     q.xproj = w.xproj; q.c = w.cbuf; q.out = sv.h; q.gates = sv.gates; q.c_all = sv.c_all;
     q.B = B; q.T = T; q.H = H;
-    for (int step = 0; step < T; ++step) {
-        q.step = step;
-        q.h_prev = w.hbuf + (size_t)(step & 1) * hn;
-        q.h_next = w.hbuf + (size_t)((step + 1) & 1) * hn;
-        HIP_TRY(launch_lstm_train_step(q, s));
-    }
+    TRY(lstm_train_run_steps(q, w.hbuf, nullptr, nullptr, T, s));  // h_0 = c_0 = 0
     TapGemmParams g = gemm1(wt->lin_w, 2 * H, 1, sv.h, (long)T * 2 * H, 1, 2 * H, logits, (long)T * V, 1, V, V, T, 2 * H);
     g.bias0 = wt->lin_b;
     HIP_TRY(launch_tap_gemm(g, B, s));
@@ -464,4 +473,69 @@ extern "C" int parrot_debug_bn_relu_bwd(const parrot_debug_bn_bwd_desc* d, void*
     bb.dgamma = d->dgamma.p; bb.dbeta = d->dbeta.p;
     bb.B = d->B; bb.C = d->C; bb.T = d->T;
     return launched(launch_bn_relu_bwd(bb, (hipStream_t)stream), who);
+}
+
+// parrot_debug_lstm: the recurrence alone, through lstm_run_steps (kernel 0, host_aligner.hip) or lstm_train_run_steps (kernel 1):
+// the loops parrot_aligner_forward and parrot_aligner_train_forward run.  Workspace: the h double buffer and c.
+namespace {
+struct LstmDebugScratch {
+    float *hbuf, *cbuf;  // [2][2][B][H], [2][B][H]
+};
+LstmDebugScratch lstm_debug_scratch(Arena& ar, int B, int H) {
+    LstmDebugScratch w{};
+    w.hbuf = ar.take<float>((size_t)2 * 2 * B * H);
+    w.cbuf = ar.take<float>((size_t)2 * B * H);
+    return w;
+}
+bool lstm_debug_sizes_ok(int B, int T, int H, int kernel) {
+    return B >= 1 && B <= 65535 && T >= 1 && T <= ALIGN_MAX_T && H >= 1 && H % 16 == 0 && H <= LSTM_MAX_DIM && (kernel == 0 || kernel == 1);
+}
+}  // namespace
+
+extern "C" size_t parrot_debug_lstm_workspace_bytes(int32_t B, int32_t T, int32_t H, int32_t kernel) {
+    if (!lstm_debug_sizes_ok(B, T, H, kernel)) return 0;
+    Arena ar(nullptr, 0);
+    (void)lstm_debug_scratch(ar, B, H);
+    return align_up(ar.off, 256);
+}
+extern "C" int parrot_debug_lstm(const float* w_hh, const float* xproj, const float* h0, const float* c0, int32_t B, int32_t T, int32_t H,
+                                 int32_t n_steps, int32_t kernel, float* out, float* h_n, float* c_n, float* gates, float* c_all, void* ws,
+                                 size_t ws_bytes, void* stream) {
+    const std::string who = "debug_lstm";
+    if (!w_hh || !xproj || !out || !h_n || !c_n || !ws) return fail(PARROT_E_INVALID, who + ": null argument");
+    if ((h0 == nullptr) != (c0 == nullptr)) return fail(PARROT_E_INVALID, who + ": h0 and c0 are given together or not at all");
+    if (kernel != 0 && kernel != 1) return fail(PARROT_E_INVALID, who + ": kernel must be 0 (lstm_step_kernel) or 1 (lstm_train_step_kernel)");
+    if (kernel == 1 && (!gates || !c_all)) return fail(PARROT_E_INVALID, who + ": kernel 1 writes gates and c_all");
+    if (kernel == 0 && (gates || c_all)) return fail(PARROT_E_INVALID, who + ": kernel 0 keeps no gates or c_all: pass NULL");
+    if (B < 1 || T < 1 || H < 1) return fail(PARROT_E_INVALID, who + ": B, T and H must be positive");
+    if (n_steps < 1 || n_steps > T) return fail(PARROT_E_INVALID, who + ": n_steps outside [1, T]");
+    if (H % 16) return fail(PARROT_E_UNSUPPORTED, who + ": H must be a multiple of 16");
+    if (H > LSTM_MAX_DIM) return fail(PARROT_E_UNSUPPORTED, who + ": H > 1024");
+    if (B > 65535) return fail(PARROT_E_UNSUPPORTED, who + ": B > 65535");
+    if (T > ALIGN_MAX_T) return fail(PARROT_E_UNSUPPORTED, who + ": T > 32768 frames");
+    Arena ar(ws, ws_bytes);
+    const LstmDebugScratch w = lstm_debug_scratch(ar, B, H);
+    if (!ar.ok) return fail(PARROT_E_UNSUPPORTED, who + ": workspace too small");
+    hipStream_t s = (hipStream_t)stream;
+    const size_t hn = (size_t)2 * B * H;
+    if (poison_word()) {  // (out, gates and c_all keep what the caller gave them outside the steps' own frames)
+        TRY(poison(ws, ws_bytes, s));
+        TRY(poison(h_n, hn * sizeof(float), s));
+        TRY(poison(c_n, hn * sizeof(float), s));
+    }
+    if (kernel == 0) {
+        LstmStepParams q{};
+        q.w_hh = w_hh; q.xproj = xproj; q.c = w.cbuf; q.out = out;
+        q.B = B; q.T = T; q.H = H;
+        TRY(lstm_run_steps(q, w.hbuf, h0, c0, n_steps, s));
+    } else {
+        LstmTrainParams q{};
+        q.w_hh[0] = w_hh; q.w_hh[1] = w_hh + (size_t)4 * H * H;
+        q.xproj = xproj; q.c = w.cbuf; q.out = out; q.gates = gates; q.c_all = c_all;
+        q.B = B; q.T = T; q.H = H;
+        TRY(lstm_train_run_steps(q, w.hbuf, h0, c0, n_steps, s));
+    }
+    HIP_TRY(hipMemcpyAsync(h_n, w.hbuf + (size_t)(n_steps & 1) * hn, hn * sizeof(float), hipMemcpyDeviceToDevice, s));
+    HIP_TRY(hipMemcpyAsync(c_n, w.cbuf, hn * sizeof(float), hipMemcpyDeviceToDevice, s));
+    return PARROT_OK;
 }

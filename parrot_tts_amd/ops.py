@@ -381,3 +381,34 @@ def debug_bn_relu_bwd(dy: torch.Tensor, x: torch.Tensor, dx: torch.Tensor, gamma
     d = _lib.DebugBnBwdDesc(*[debug_buf(t) for t in (dy, x, dx, gamma, mean, invstd, dgamma, dbeta)], B, C_, T)
     with torch.cuda.device(x.device):
         _lib.check(_lib.lib().parrot_debug_bn_relu_bwd(C.byref(d), stream_ptr(x.device)))
+
+
+def debug_lstm(w_hh: torch.Tensor, xproj: torch.Tensor, kernel: int, h0: Optional[torch.Tensor] = None, c0: Optional[torch.Tensor] = None,
+               n_steps: Optional[int] = None, out: Optional[torch.Tensor] = None) -> dict:
+    """The aligner's LSTM recurrence on its own, through the step loop of the inference forward (``kernel`` 0, lstm_step_kernel) or of
+    the training forward (1, lstm_train_step_kernel) (tests; include/parrot_hip_debug.h): w_hh (2, 4H, H), xproj (B, T, 8H), h0 / c0
+    (2, B, H) or None for zeros -> {"out" (B, T, 2H), "h_n", "c_n" (2, B, H), and for kernel 1 "gates" (B, T, 8H), "c_all" (B, T, 2H)}.
+    ``n_steps`` < T runs the first steps only; ``out``: a caller-filled tensor whose other frames are left alone."""
+    require_cuda(xproj, "xproj")
+    dev = xproj.device
+    assert xproj.dim() == 3 and w_hh.dim() == 3
+    B, T, H = int(xproj.shape[0]), int(xproj.shape[1]), int(w_hh.shape[2])
+    _dev_arg(w_hh, torch.float32, (2, 4 * H, H), dev, "w_hh")
+    _dev_arg(xproj, torch.float32, (B, T, 8 * H), dev, "xproj")
+    _dev_arg(h0, torch.float32, (2, B, H), dev, "h0")
+    _dev_arg(c0, torch.float32, (2, B, H), dev, "c0")
+    if out is None:
+        out = torch.empty((B, T, 2 * H), dtype=torch.float32, device=dev)
+    _dev_arg(out, torch.float32, (B, T, 2 * H), dev, "out")
+    res = {"out": out, "h_n": torch.empty((2, B, H), dtype=torch.float32, device=dev), "c_n": torch.empty((2, B, H), dtype=torch.float32, device=dev)}
+    if kernel == 1:
+        res["gates"] = torch.empty((B, T, 8 * H), dtype=torch.float32, device=dev)
+        res["c_all"] = torch.empty((B, T, 2 * H), dtype=torch.float32, device=dev)
+    lib = _lib.lib()
+    n_ws = int(lib.parrot_debug_lstm_workspace_bytes(B, T, H, int(kernel)))
+    ws = _workspace(n_ws, dev)
+    with torch.cuda.device(dev):
+        _lib.check(lib.parrot_debug_lstm(dptr(w_hh), dptr(xproj), dptr(h0), dptr(c0), B, T, H, T if n_steps is None else int(n_steps), int(kernel),
+                                         dptr(out), dptr(res["h_n"]), dptr(res["c_n"]), dptr(res.get("gates")), dptr(res.get("c_all")), dptr(ws),
+                                         n_ws, stream_ptr(dev)))
+    return res

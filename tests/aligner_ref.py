@@ -37,6 +37,41 @@ def lstm_direction(x, w_ih, w_hh, b_ih, b_hh, reverse: bool):
     return out
 
 
+def lstm_steps(w_hh, xproj, h0=None, c0=None, n_steps=None, dtype=torch.float64):
+    """The recurrence of ``lstm_direction`` for both directions at once, started from a given state and stopped after ``n_steps``:
+    w_hh (2, 4H, H) [forward, backward], xproj (B, T, 8H) = W_ih x + b_ih + b_hh of both directions, h0 / c0 (2, B, H) or None for
+    zeros -> out (B, T, 2H), h_n, c_n (2, B, H), gates (B, T, 8H) = sigmoid(i), sigmoid(f), tanh(g), sigmoid(o) per direction, c_all
+    (B, T, 2H), all in ``dtype``.  The forward direction takes frames 0 .. n_steps - 1, the backward one T - 1 .. T - n_steps; frames
+    no step owns are zero.  The pre-activation is xproj[:, t] + h W_hh^T: ``lstm_direction``'s with b_hh already inside xproj."""
+    w_hh, xproj = torch.as_tensor(w_hh).to(dtype), torch.as_tensor(xproj).to(dtype)
+    B, T, H = xproj.shape[0], xproj.shape[1], w_hh.shape[2]
+    n_steps = T if n_steps is None else int(n_steps)
+    assert w_hh.shape == (2, 4 * H, H) and xproj.shape == (B, T, 8 * H) and 1 <= n_steps <= T
+    h_n = xproj.new_zeros(2, B, H) if h0 is None else torch.as_tensor(h0).to(dtype).clone()
+    c_n = xproj.new_zeros(2, B, H) if c0 is None else torch.as_tensor(c0).to(dtype).clone()
+    out, c_all, gates = xproj.new_zeros(B, T, 2 * H), xproj.new_zeros(B, T, 2 * H), xproj.new_zeros(B, T, 8 * H)
+    for d in range(2):
+        h, c = h_n[d], c_n[d]
+        for step in range(n_steps):
+            t = T - 1 - step if d else step
+            g = xproj[:, t, d * 4 * H:(d + 1) * 4 * H] + (h @ w_hh[d].t())
+            i_, f_, g_, o_ = torch.sigmoid(g[:, :H]), torch.sigmoid(g[:, H:2 * H]), torch.tanh(g[:, 2 * H:3 * H]), torch.sigmoid(g[:, 3 * H:])
+            c = f_ * c + i_ * g_
+            h = o_ * torch.tanh(c)
+            out[:, t, d * H:(d + 1) * H] = h
+            c_all[:, t, d * H:(d + 1) * H] = c
+            gates[:, t, d * 4 * H:(d + 1) * 4 * H] = torch.cat([i_, f_, g_, o_], dim=1)
+        h_n[d], c_n[d] = h, c
+    return out, h_n, c_n, gates, c_all
+
+
+def lstm_preactivations(w_hh, xproj, h0, dtype=torch.float64):
+    """The gate pre-activations of step 0 of ``lstm_steps`` from h0 (2, B, H): (2, B, 4H), forward direction at frame 0, backward at T - 1."""
+    w_hh, xproj, h0 = (torch.as_tensor(v).to(dtype) for v in (w_hh, xproj, h0))
+    T, H = xproj.shape[1], w_hh.shape[2]
+    return torch.stack([xproj[:, T - 1 if d else 0, d * 4 * H:(d + 1) * 4 * H] + (h0[d] @ w_hh[d].t()) for d in range(2)])
+
+
 def aligner_forward(sd: dict, mel: torch.Tensor):
     """mel (B, T, n_mels) -> (logits (B, T, V), {"bn3": (B, T, conv_dim), "lstm": (B, T, 2 lstm_dim)}) in mel's dtype, from the fp32
     state_dict the reference holds.  The whole padded batch, no masking (model.py:41-48)."""
@@ -121,6 +156,38 @@ def dp_durations(tokens: np.ndarray, pred: np.ndarray, with_info: bool = False):
     if with_info:
         return dur, float(dist[T - 1, N - 1]), bool(unique)
     return dur
+
+
+def dp_durations_fast(tokens: np.ndarray, pred: np.ndarray):
+    """``dp_durations`` for sizes where ``dp_tables``' Python double loop is too slow (2100 x 2048): the same fp64 programme swept along
+    the anti-diagonals i + j = d with numpy -- the same three predecessor reads (+inf outside the grid), the same tie rule (diagonal,
+    then previous frame, then previous token), the same best + w and the same backward walk -> (durations (N,) int32, cost)."""
+    w = path_weights(tokens, pred)
+    T, N = w.shape
+    D = np.full((T + 1, N + 1), np.inf, dtype=np.float64)  # D[i + 1][j + 1] = dist[i][j]; row 0 and column 0 stand for "outside"
+    move = np.zeros((T, N), dtype=np.int8)
+    D[1, 1] = 0.0
+    for d in range(1, T + N - 1):
+        j = np.arange(max(0, d - (T - 1)), min(N - 1, d) + 1)
+        i = d - j
+        dg, up, lf = D[i, j], D[i, j + 1], D[i + 1, j]
+        m = np.where((dg <= up) & (dg <= lf), 0, np.where(up <= lf, 1, 2))
+        best = np.where(m == 0, dg, np.where(m == 1, up, lf))
+        D[i + 1, j + 1] = best + w[i, j]
+        move[i, j] = m
+    dur = np.zeros(N, dtype=np.int32)
+    i, j = T - 1, N - 1
+    dur[j] += 1
+    while i > 0 or j > 0:
+        m = move[i, j]
+        if m == 2:
+            j -= 1
+        else:
+            i -= 1
+            if m == 0:
+                j -= 1
+            dur[j] += 1
+    return dur, float(D[T, N])
 
 
 def path_cost(durations: np.ndarray, tokens: np.ndarray, pred: np.ndarray) -> float:

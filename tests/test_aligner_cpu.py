@@ -98,6 +98,85 @@ def test_dp_restatement_against_the_reference(golden_dir):
     assert by["t17n1"][3].tolist() == [17]
 
 
+@pytest.mark.parametrize("dtype", [torch.float32, torch.float64])
+def test_lstm_steps_is_lstm_direction_from_a_zero_state(dtype):
+    """``lstm_steps`` -- what tests/test_gpu_aligner_kernels.py holds the two LSTM step kernels to -- from a zero state with
+    n_steps = T is ``lstm_direction`` / the "lstm" tap of ``aligner_forward`` EXACTLY, in both dtypes, once bias_hh is folded into
+    the input projection as the library folds it (bias_hh = 0 here, so both add the same two numbers); with the fixture's own
+    bias_hh, which ``lstm_direction`` adds to h W_hh^T first, the two agree to rounding.  A run stopped after n_steps and resumed
+    from its state is the full run; frames no step owns stay zero."""
+    m = dict(n_mels=24, lstm_dim=48, conv_dim=32, num_symbols=13)
+    cfg = synth.default_aligner_config()
+    cfg["audio"]["n_mels"] = m["n_mels"]
+    cfg["model"].update(lstm_dim=m["lstm_dim"], conv_dim=m["conv_dim"])
+    sd = synth.synth_aligner_state_dict(cfg, m["num_symbols"], seed=21, gain=2.0)
+    mel = synth.synth_aligner_mel(3, 11, m["n_mels"], seed=22).to(dtype)
+    H = m["lstm_dim"]
+
+    def xproj_of(sd):
+        bn3 = R.aligner_forward(sd, mel)[1]["bn3"]
+        return torch.cat([bn3 @ sd["rnn.weight_ih_l0" + s].to(dtype).t() + sd["rnn.bias_ih_l0" + s].to(dtype) + sd["rnn.bias_hh_l0" + s].to(dtype)
+                          for s in ("", "_reverse")], dim=-1)
+
+    w_hh = torch.stack([sd["rnn.weight_hh_l0"], sd["rnn.weight_hh_l0_reverse"]])
+    folded = dict(sd)
+    for s in ("", "_reverse"):
+        folded["rnn.bias_hh_l0" + s] = torch.zeros_like(sd["rnn.bias_hh_l0" + s])
+    assert any(bool(sd["rnn.bias_ih_l0" + s].abs().max() > 0) for s in ("", "_reverse"))
+    want = R.aligner_forward(folded, mel)[1]["lstm"]
+    out, h_n, c_n, gates, c_all = R.lstm_steps(w_hh, xproj_of(folded), None, None, None, dtype)
+    assert out.dtype == dtype and torch.equal(out, want)
+    assert torch.equal(h_n[0], out[:, -1, :H]) and torch.equal(h_n[1], out[:, 0, H:])
+    assert torch.equal(c_n[0], c_all[:, -1, :H]) and torch.equal(c_n[1], c_all[:, 0, H:])
+    o_ = torch.cat([gates[..., 3 * H:4 * H], gates[..., 7 * H:]], dim=-1)
+    assert torch.equal(out, o_ * torch.tanh(c_all))
+    # the fixture's own bias_hh: another order of the same three-term sum
+    want = R.aligner_forward(sd, mel)[1]["lstm"]
+    full = R.lstm_steps(w_hh, xproj_of(sd), None, None, None, dtype)
+    assert float((full[0] - want).abs().max()) <= (1e-12 if dtype == torch.float64 else 1e-5)
+    # stopped after 4 steps and resumed: the forward direction continues on frames 4 .., the backward one on frames .. T - 5
+    xp = xproj_of(sd)
+    T = xp.shape[1]
+    first = R.lstm_steps(w_hh, xp, None, None, 4, dtype)
+    assert not first[0][:, 4:, :H].any() and not first[0][:, :T - 4, H:].any()
+    assert torch.equal(first[0][:, :4, :H], full[0][:, :4, :H]) and torch.equal(first[0][:, T - 4:, H:], full[0][:, T - 4:, H:])
+    rest = torch.cat([xp[:, 4:, :4 * H], xp[:, :T - 4, 4 * H:]], dim=-1)
+    second = R.lstm_steps(w_hh, rest, first[1], first[2], None, dtype)
+    assert torch.equal(second[0][..., :H], full[0][:, 4:, :H]) and torch.equal(second[0][..., H:], full[0][:, :T - 4, H:])
+    assert torch.equal(second[1], full[1]) and torch.equal(second[2], full[2])
+    pre = R.lstm_preactivations(w_hh, rest, first[1], dtype)
+    assert torch.equal(torch.sigmoid(pre[0][:, :H]), second[3][:, 0, :H]) and torch.equal(torch.tanh(pre[1][:, 2 * H:3 * H]), second[3][:, -1, 6 * H:7 * H])
+
+
+def _fast_dp_seeded_cases():
+    """(name, tokens, pred): (1, 9), (9, 1), (40, 33) uniform (every cell tied), (50, 20) saturated (w exactly 0 or 1)."""
+    rng = np.random.Generator(np.random.PCG64(31))
+    V = 11
+    soft = lambda T: torch.softmax(torch.from_numpy(rng.standard_normal((T, V)) * 3), -1).numpy().astype(np.float32)  # noqa: E731
+    cases = [("t1n9", rng.integers(0, V, 9), soft(1)), ("t9n1", rng.integers(0, V, 1), soft(9)),
+             ("t40n33_uniform", rng.integers(0, V, 33), np.full((40, V), 1.0 / V, np.float32))]
+    sat = np.zeros((50, V), np.float32)
+    sat[np.arange(50), rng.integers(0, V, 50)] = 1.0
+    cases.append(("t50n20_saturated", rng.integers(0, V, 20), sat))
+    return cases
+
+
+def test_fast_dp_is_the_slow_dp(golden_dir):
+    """``dp_durations_fast`` (the anti-diagonal sweep the GPU tests use at 2100 x 2048) gives ``dp_durations``' durations and its cost
+    bit for bit: on every case of align_dp.npz, on single-frame and single-token grids, with every cell tied, and saturated."""
+    z, m = R.load_golden(golden_dir, R.DP_GOLDEN)
+    cases = [(c, z[c + "_tokens"], z[c + "_pred"]) for c in m["cases"]] + _fast_dp_seeded_cases()
+    assert len(cases) >= 10
+    for name, tokens, pred in cases:
+        dur, cost, _ = R.dp_durations(tokens, pred, with_info=True)
+        fdur, fcost = R.dp_durations_fast(tokens, pred)
+        assert fdur.dtype == np.int32 and np.array_equal(fdur, dur), name
+        assert np.float64(fcost).tobytes() == np.float64(cost).tobytes(), name
+        assert int(fdur.sum()) == pred.shape[0], name
+    w = R.path_weights(cases[-1][1], cases[-1][2])
+    assert set(np.unique(w).tolist()) <= {0.0, 1.0}
+
+
 def test_state_dict_round_trip_and_from_checkpoint():
     cfg = synth.small_aligner_config()
     symbols = list("abcdefghijklmnopqrst")
