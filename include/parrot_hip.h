@@ -568,6 +568,77 @@ int parrot_aligner_train_backward(const parrot_aligner_cfg* cfg, const parrot_al
                                   const float* grad_logits, int32_t B, int32_t T, const parrot_aligner_grads* grads, void* ws, size_t ws_bytes,
                                   void* stream);
 
+/* ---- training the TTE (modules/parrot.py:90-110 with inference=False under model.train(); train.py:72-85) ----
+ * The teacher-forced forward with dropout and the full backward, as two stateless calls shaped like the aligner's.  Every weight is
+ * read from the DEVICE pointer given here, in torch's layout: nothing is packed, cached or copied to the host, neither call
+ * synchronises, and a parameter an optimiser has just updated in place is seen by the next call.
+ *   forward: tok_emb[phones] + pe[S] (the single row of the padded length, fft.py:18) -> the encoder FFT blocks under src_mask ->
+ *   + speaker_emb[speaker] (n_speaker > 1) -> the duration predictor on that output, masked to 0 outside src_mask -> the length
+ *   regulator on the CALLER's durations (every position counts; rows shorter than L are zero-padded) -> + pe[L] -> the decoder
+ *   blocks under tgt_mask -> the head.  phones, duration (B, S) i64; src_mask (B, S), tgt_mask (B, L) u8, 1 = attend; speaker (B) i64
+ *   (NULL without a speaker embedding); logits (B, L, n_codes), log_dur (B, S) f32.  The caller checks what torch would raise on:
+ *   ids inside their tables, durations >= 0 with max row sum == L (an id outside its table gives NaN rows here, never an access
+ *   through it; durations are saturated into [0, L]).
+ *   training != 0: dropout acts on the softmax probabilities of every FFT block (p_enc / p_dec) and after the two LayerNorms of the
+ *   duration predictor (p_dp), nowhere else.  Element i of dropout site `site` is kept iff
+ *       philox4x32_10(counter {lo32(i), hi32(i), lo32(offset), (hi32(offset) & 0xffffff) | site << 24}, key {lo32(seed), hi32(seed)})[0] >> 8
+ *           >= floor(p 2^24 + 0.5)
+ *   and a survivor is multiplied by the fp32 quotient 1 / (1 - p); p = 0 is the identity, p = 1 gives zeros.  Sites: 0, 1 the
+ *   duration predictor's (i = (b S + s) n_filter + c), 2 + l encoder block l, 2 + enc_layers + l decoder block l
+ *   (i = ((b H + h) T + tq) T + tk).  The backward regenerates the masks from (seed, offset): they are not stored.
+ *   saved (parrot_tte_train_saved_bytes; may be NULL when training == 0) keeps every activation the backward reads, the softmax
+ *   probabilities before dropout among them: about B (S (14 D + F) + 2 H S^2) floats per encoder block, the same with L per decoder
+ *   block.  The weight-gradient partials in the workspace are bounded by max(64 MiB, ceil(B max(S, L) / 256) x the largest one-tap
+ *   weight): wider convs are reduced a few taps at a time.
+ * backward: the gradient of every parameter from grad_logits (B, L, n_codes) and grad_log_dur (B, S); either may be NULL (zero).
+ * All products are exact fp32 (fp32 MFMA, fp32 accumulation); every gradient that sums over B T (weights, biases, gamma, beta, the
+ * embedding rows, the length regulator's segments) is summed in fp64 in a fixed order and rounded once.  No floating-point atomics:
+ * two calls on the same inputs and (seed, offset) agree bit for bit.  NaN / inf propagate.  Limits (PARROT_E_INVALID): at most
+ * PARROT_TTE_TRAIN_MAX_LAYERS blocks per stack, odd FFN kernels of at most 9 taps, duration kernel 3, B x heads <= 65535,
+ * B max(S, L) <= 1 863 936; max(S, L) >= max_len is PARROT_E_RANGE (pe[T]), before any launch. */
+#define PARROT_TTE_TRAIN_MAX_LAYERS 16
+typedef struct {
+    parrot_tte_cfg tte;
+    int32_t pad_idx;             /* tok_emb's padding_idx: that row's gradient is exactly 0; -1 = none */
+    float p_enc, p_dec, p_dp;    /* the three dropout probabilities */
+} parrot_tte_train_cfg;
+typedef struct {
+    const float *pe, *tok_emb, *speaker_emb;   /* the fields of parrot_tte_weights, as fp32 DEVICE pointers */
+    const float *dp_conv0_w, *dp_conv0_b, *dp_ln0_w, *dp_ln0_b;
+    const float *dp_conv1_w, *dp_conv1_b, *dp_ln1_w, *dp_ln1_b;
+    const float *dp_proj_w, *dp_proj_b;
+    const float *head_w, *head_b;
+    parrot_fft_weights enc[PARROT_TTE_TRAIN_MAX_LAYERS];
+    parrot_fft_weights dec[PARROT_TTE_TRAIN_MAX_LAYERS];
+} parrot_tte_dev_weights;
+typedef struct {
+    float *qkv, *in_proj, *out_proj, *wo;
+    float *conv1_w, *conv1_b, *conv2_w, *conv2_b;
+    float *attn_norm_w, *attn_norm_b, *conv_norm_w, *conv_norm_b;
+} parrot_fft_grads;
+/* Where the backward writes d loss / d parameter: device, the parameter's own shape.  A null field is not computed; pe is a
+ * buffer and is never written. */
+typedef struct {
+    float *pe, *tok_emb, *speaker_emb;
+    float *dp_conv0_w, *dp_conv0_b, *dp_ln0_w, *dp_ln0_b;
+    float *dp_conv1_w, *dp_conv1_b, *dp_ln1_w, *dp_ln1_b;
+    float *dp_proj_w, *dp_proj_b;
+    float *head_w, *head_b;
+    parrot_fft_grads enc[PARROT_TTE_TRAIN_MAX_LAYERS];
+    parrot_fft_grads dec[PARROT_TTE_TRAIN_MAX_LAYERS];
+} parrot_tte_grads;
+/* Bytes of what the forward keeps for the backward, and of the workspace of either call (0 beyond the limits). */
+size_t parrot_tte_train_saved_bytes(const parrot_tte_train_cfg* cfg, int32_t B, int32_t S, int32_t L);
+size_t parrot_tte_train_workspace_bytes(const parrot_tte_train_cfg* cfg, int32_t B, int32_t S, int32_t L);
+int parrot_tte_train_forward(const parrot_tte_train_cfg* cfg, const parrot_tte_dev_weights* w, const int64_t* phones, const uint8_t* src_mask,
+                             const int64_t* speaker, const int64_t* duration, const uint8_t* tgt_mask, int32_t B, int32_t S, int32_t L,
+                             int32_t training, uint64_t seed, uint64_t offset, float* logits, float* log_dur, void* saved, void* ws,
+                             size_t ws_bytes, void* stream);
+int parrot_tte_train_backward(const parrot_tte_train_cfg* cfg, const parrot_tte_dev_weights* w, const int64_t* phones, const uint8_t* src_mask,
+                              const int64_t* speaker, const int64_t* duration, const uint8_t* tgt_mask, const void* saved,
+                              const float* grad_logits, const float* grad_log_dur, int32_t B, int32_t S, int32_t L, uint64_t seed,
+                              uint64_t offset, const parrot_tte_grads* grads, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- the vocoder's adversarial losses (utils/vocoder/models.py:279-310; train.py:141-148, 159-165) ----
  * feature_loss, generator_loss and discriminator_loss are sums of means over dense fp32 arrays.  One call evaluates a whole
  * table of such TERMS -- the 54 feature maps and 8 scores of a generator step, say -- with their gradients: one launch reads

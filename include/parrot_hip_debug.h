@@ -166,6 +166,37 @@ size_t parrot_debug_lstm_workspace_bytes(int32_t B, int32_t T, int32_t H, int32_
 int parrot_debug_lstm(const float* w_hh, const float* xproj, const float* h0, const float* c0, int32_t B, int32_t T, int32_t H,
                       int32_t n_steps, int32_t kernel, float* out, float* h_n, float* c_n, float* gates, float* c_all, void* ws,
                       size_t ws_bytes, void* stream);
+/* Tests: the dropout mask parrot_tte_train_forward / _backward apply at `site` under (seed, offset) with probability p (the rule:
+ * parrot_hip.h), elements 0 .. n - 1: out_u8[i] = 1 kept, 0 dropped (DEVICE, n bytes).  site in [0, 255], 0 <= p <= 1. */
+int parrot_tte_train_dropout_mask(uint64_t seed, uint64_t offset, int32_t site, int64_t n, float p, uint8_t* out_u8, void* stream);
+/* Tests: the TTE's training kernels (csrc/tte_train.h) alone, on caller-owned dense DEVICE buffers whose sizes follow from the
+ * dimensions given; dropout arguments as parrot_tte_train_dropout_mask's.  A null argument or a size below 1: PARROT_E_INVALID.
+ *   ln_fwd            x (rows, C) -> y, mean (rows), rstd (rows)
+ *   ln_bwd            dx (rows, C) = LayerNorm's data gradient of dy + res (nullable), 0 where relu_mask and x <= 0; dyxh = dy xhat
+ *   softmax_drop_fwd  scores (B, H, T, T) -> P in place under key_valid (B, T); pd (nullable): P after dropout
+ *   softmax_drop_bwd  dP (B, H, T, T), the gradient at the dropped probabilities, -> dS in place
+ *   dropout           y[i] = keep(i) ? x[i] / (1 - p) : 0, i < n; p = 0 copies
+ *   lr_bwd            denc (B, S, D) = the segment sums of dy (B, L, D) under dur (B, S) i64 (+ add, nullable); cum: (B, S + 1) i32 scratch
+ *   embed_grad        dtab (V, D) = sum over rows r with ids[r / per] == v of dx (rows, D); row pad_idx (if >= 0) exactly 0
+ *   conv_dw           dW (cout, cin, kk) of conv1d(X (B, T, cin), W, padding = pad) from dY (B, T, cout), reduced `group` taps at a
+ *                     time (1 <= group <= kk <= 9): group < kk is the path a weight gradient takes when its partials exceed the
+ *                     workspace bound.  ws: parrot_debug_tte_conv_dw_workspace_bytes (0 for sizes that are not valid). */
+int parrot_debug_tte_ln_fwd(const float* x, const float* gamma, const float* beta, float* y, float* mean, float* rstd, int64_t rows, int32_t C,
+                            void* stream);
+int parrot_debug_tte_ln_bwd(const float* dy, const float* x, const float* gamma, const float* mean, const float* rstd, const float* res, float* dx,
+                            float* dyxh, int64_t rows, int32_t C, int32_t relu_mask, void* stream);
+int parrot_debug_tte_softmax_drop_fwd(float* scores, float* pd, const uint8_t* key_valid, int32_t B, int32_t H, int32_t T, float p, uint64_t seed,
+                                      uint64_t offset, int32_t site, void* stream);
+int parrot_debug_tte_softmax_drop_bwd(const float* P, float* dP, int32_t B, int32_t H, int32_t T, float p, uint64_t seed, uint64_t offset,
+                                      int32_t site, void* stream);
+int parrot_debug_tte_dropout(const float* x, float* y, int64_t n, float p, uint64_t seed, uint64_t offset, int32_t site, void* stream);
+int parrot_debug_tte_lr_bwd(const float* dy, const int64_t* dur, const float* add, float* denc, int32_t* cum, int32_t B, int32_t S, int32_t L,
+                            int32_t D, void* stream);
+int parrot_debug_tte_embed_grad(const int64_t* ids, const float* dx, float* dtab, int64_t rows, int32_t per, int32_t D, int32_t V, int32_t pad_idx,
+                                void* stream);
+size_t parrot_debug_tte_conv_dw_workspace_bytes(int32_t cout, int32_t cin, int32_t kk, int32_t B, int32_t T, int32_t group);
+int parrot_debug_tte_conv_dw(const float* dY, const float* X, float* dW, int32_t cout, int32_t cin, int32_t kk, int32_t pad, int32_t B, int32_t T,
+                             int32_t group, void* ws, size_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }

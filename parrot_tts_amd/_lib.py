@@ -85,6 +85,25 @@ class AlignerGrads(C.Structure):  # parrot_aligner_grads: where the backward wri
                [(n, C.c_void_p * 2) for n in ("w_ih", "w_hh", "b_ih", "b_hh")] + [("lin_w", C.c_void_p), ("lin_b", C.c_void_p)]
 
 
+TTE_TRAIN_MAX_LAYERS = 16  # PARROT_TTE_TRAIN_MAX_LAYERS of include/parrot_hip.h
+FFT_FIELDS = ("qkv", "in_proj", "out_proj", "wo", "conv1_w", "conv1_b", "conv2_w", "conv2_b", "attn_norm_w", "attn_norm_b", "conv_norm_w",
+              "conv_norm_b")
+TTE_TOP_FIELDS = ("pe", "tok_emb", "speaker_emb", "dp_conv0_w", "dp_conv0_b", "dp_ln0_w", "dp_ln0_b", "dp_conv1_w", "dp_conv1_b", "dp_ln1_w",
+                  "dp_ln1_b", "dp_proj_w", "dp_proj_b", "head_w", "head_b")
+
+
+class TteTrainCfg(C.Structure):  # parrot_tte_train_cfg
+    _fields_ = [("tte", TteCfg), ("pad_idx", C.c_int32), ("p_enc", C.c_float), ("p_dec", C.c_float), ("p_dp", C.c_float)]
+
+
+class FftDevPtrs(C.Structure):  # parrot_fft_weights with DEVICE pointers / parrot_fft_grads: the same layout
+    _fields_ = [(n, C.c_void_p) for n in FFT_FIELDS]
+
+
+class TteDevPtrs(C.Structure):  # parrot_tte_dev_weights / parrot_tte_grads: the same layout
+    _fields_ = [(n, C.c_void_p) for n in TTE_TOP_FIELDS] + [("enc", FftDevPtrs * TTE_TRAIN_MAX_LAYERS), ("dec", FftDevPtrs * TTE_TRAIN_MAX_LAYERS)]
+
+
 class GanTerm(C.Structure):  # parrot_gan_term_t: 48 bytes
     _fields_ = [("a", C.c_void_p), ("b", C.c_void_p), ("grad_a", C.c_void_p), ("grad_b", C.c_void_p), ("n", C.c_int64),
                 ("op", C.c_int32), ("reserved", C.c_int32)]
@@ -226,6 +245,22 @@ SIGNATURES = {
     "parrot_aligner_train_forward": (C.c_int, [C.POINTER(AlignerCfg), C.POINTER(AlignerDevWeights), vp, i32, i32, i32, vp, vp, vp, sz, vp]),
     "parrot_aligner_train_backward": (C.c_int, [C.POINTER(AlignerCfg), C.POINTER(AlignerDevWeights), vp, vp, vp, i32, i32,
                                                 C.POINTER(AlignerGrads), vp, sz, vp]),
+    "parrot_tte_train_saved_bytes": (sz, [C.POINTER(TteTrainCfg), i32, i32, i32]),
+    "parrot_tte_train_workspace_bytes": (sz, [C.POINTER(TteTrainCfg), i32, i32, i32]),
+    "parrot_tte_train_forward": (C.c_int, [C.POINTER(TteTrainCfg), C.POINTER(TteDevPtrs), vp, vp, vp, vp, vp, i32, i32, i32, i32, C.c_uint64,
+                                           C.c_uint64, vp, vp, vp, vp, sz, vp]),
+    "parrot_tte_train_backward": (C.c_int, [C.POINTER(TteTrainCfg), C.POINTER(TteDevPtrs), vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32,
+                                            C.c_uint64, C.c_uint64, C.POINTER(TteDevPtrs), vp, sz, vp]),
+    "parrot_tte_train_dropout_mask": (C.c_int, [C.c_uint64, C.c_uint64, i32, C.c_int64, f32, vp, vp]),
+    "parrot_debug_tte_ln_fwd": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_int64, i32, vp]),
+    "parrot_debug_tte_ln_bwd": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, C.c_int64, i32, i32, vp]),
+    "parrot_debug_tte_softmax_drop_fwd": (C.c_int, [vp, vp, vp, i32, i32, i32, f32, C.c_uint64, C.c_uint64, i32, vp]),
+    "parrot_debug_tte_softmax_drop_bwd": (C.c_int, [vp, vp, i32, i32, i32, f32, C.c_uint64, C.c_uint64, i32, vp]),
+    "parrot_debug_tte_dropout": (C.c_int, [vp, vp, C.c_int64, f32, C.c_uint64, C.c_uint64, i32, vp]),
+    "parrot_debug_tte_lr_bwd": (C.c_int, [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]),
+    "parrot_debug_tte_embed_grad": (C.c_int, [vp, vp, vp, C.c_int64, i32, i32, i32, i32, vp]),
+    "parrot_debug_tte_conv_dw_workspace_bytes": (sz, [i32, i32, i32, i32, i32, i32]),
+    "parrot_debug_tte_conv_dw": (C.c_int, [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, sz, vp]),
     "parrot_debug_tap_gemm": (C.c_int, [C.POINTER(DebugTapGemmDesc), vp]),
     "parrot_debug_wgrad_workspace_bytes": (sz, [i32, i32, i32, i32]),
     "parrot_debug_wgrad": (C.c_int, [C.POINTER(DebugWgradDesc), vp, sz, vp]),

@@ -20,13 +20,18 @@ from .vocoder import AttrDict, CodeGenerator
 
 class LitParrot(nn.Module):
     """Stand-in for the reference's LightningModule wrapper (inference.py:10-23, train.py:61-95): holds ``self.parrot`` and
-    ``self.loss_fn``, ``infer`` switches to eval mode first, ``validation_step`` is the reference's, ``load_from_checkpoint``
-    understands Lightning's layout."""
+    ``self.loss_fn``, ``infer`` switches to eval mode first, ``training_step`` and ``validation_step`` are the reference's,
+    ``load_from_checkpoint`` understands Lightning's layout.  ``trainable=True`` holds a ``TrainableParrot`` (tte_train.py: the training
+    forward with its backward; no ``infer``) instead of the inference ``Parrot``; the checkpoint keys are the same."""
 
-    def __init__(self, data_config, src_vocab_size, src_pad_idx):
+    def __init__(self, data_config, src_vocab_size, src_pad_idx, trainable: bool = False):
         super().__init__()
         self.hparams = AttrDict(data_config=data_config, src_vocab_size=src_vocab_size, src_pad_idx=src_pad_idx)
-        self.parrot = Parrot(data_config, src_vocab_size, src_pad_idx)
+        if trainable:
+            from .tte_train import TrainableParrot
+            self.parrot = TrainableParrot(data_config, src_vocab_size, src_pad_idx)
+        else:
+            self.parrot = Parrot(data_config, src_vocab_size, src_pad_idx)
         self.loss_fn = ModelLoss(data_config)
         self.logged = {}  # what `log` received (Lightning is not a dependency: the values are kept under their names)
 
@@ -35,6 +40,16 @@ class LitParrot(nn.Module):
 
     def log(self, name, value, **kwargs):
         self.logged[name] = value
+
+    def training_step(self, batch, batch_idx):
+        """train.py:72-85: the training forward and ModelLoss; returns the total loss with its graph, logs the three values (the
+        learning rate is the driver's to log: there is no ``self.trainer`` here)."""
+        out, _, _, log_dur_preds = self.parrot(batch)
+        total_loss, code_loss, dur_loss = self.loss_fn(out, log_dur_preds, batch)
+        self.log("train_total_loss", total_loss, prog_bar=True)
+        self.log("train_code_loss", code_loss, prog_bar=True)
+        self.log("train_dur_loss", dur_loss, prog_bar=True)
+        return total_loss
 
     def validation_step(self, batch, batch_idx):
         """train.py:87-95: the teacher-forced forward and ModelLoss; returns the total loss, logs the three values."""

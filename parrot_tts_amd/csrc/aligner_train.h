@@ -20,7 +20,7 @@
 
 namespace parrot {
 
-constexpr int AT_MAX_TAPS = 5;
+constexpr int AT_MAX_TAPS = 9;     // the widest conv that goes through tap_gemm_kernel: the TTE's k = 9 FFN conv (the aligner's have 5)
 constexpr int AT_RCHUNK = 256;    // (b, t) pairs per weight-gradient / column-sum partial: the fixed block of the two-level sums
 constexpr int AT_ACC_FLUSH = 8;   // tap_gemm_kernel moves its accumulator into a second one every 8 x 32 products
 constexpr int AT_BT = 16;         // batch rows per pass of the LSTM step kernels: their sums live in registers, nothing is staged in LDS

@@ -13,7 +13,8 @@ using namespace parrot;
 
 namespace {
 
-constexpr long AT_MAX_BT = (long)(65535 / AT_MAX_TAPS) * AT_RCHUNK;  // wgrad_kernel's grid.z = chunks x taps
+constexpr int ALIGNER_TAPS = 5;  // the aligner's convs; also the slots of the debug descriptors
+constexpr long AT_MAX_BT = (long)(65535 / ALIGNER_TAPS) * AT_RCHUNK;  // wgrad_kernel's grid.z = chunks x taps
 
 // What the forward keeps for the backward.  Activations are channel-first (B, C, T) around the convs, (B, T, C) around the LSTM.
 struct TrainSaved {
@@ -323,7 +324,7 @@ extern "C" int parrot_aligner_train_backward(const parrot_aligner_cfg* cfg, cons
 // ---------------------------------------------------------------------------------------------
 namespace {
 
-static_assert(PARROT_DEBUG_MAX_TAPS == AT_MAX_TAPS, "the debug descriptors hold one slot per tap");
+static_assert(PARROT_DEBUG_MAX_TAPS == ALIGNER_TAPS && ALIGNER_TAPS <= AT_MAX_TAPS, "the debug descriptors hold one slot per tap");
 
 // smallest and largest element index of sum_i idx_i stride_i + offset, idx_i in [lo_i, hi_i]
 struct Reach {
@@ -349,7 +350,7 @@ int launched(hipError_t e, const std::string& who) {
     if (e != hipSuccess) return fail(PARROT_E_HIP, who + ": " + hipGetErrorString(e));
     return PARROT_OK;
 }
-bool wgrad_sizes_ok(long R, long ntaps, long M, long K) { return R >= 1 && ntaps >= 1 && ntaps <= AT_MAX_TAPS && M >= 1 && K >= 1; }
+bool wgrad_sizes_ok(long R, long ntaps, long M, long K) { return R >= 1 && ntaps >= 1 && ntaps <= PARROT_DEBUG_MAX_TAPS && M >= 1 && K >= 1; }
 
 }  // namespace
 
@@ -357,7 +358,7 @@ extern "C" int parrot_debug_tap_gemm(const parrot_debug_tap_gemm_desc* d, void* 
     const std::string who = "debug_tap_gemm";
     if (!d) return fail(PARROT_E_INVALID, who + ": null argument");
     if (d->ntaps < 1 || d->M < 1 || d->N < 1 || d->K < 1 || d->Z < 1) return fail(PARROT_E_INVALID, who + ": ntaps, M, N, K and Z must be positive");
-    if (d->ntaps > AT_MAX_TAPS) return fail(PARROT_E_UNSUPPORTED, who + ": more than 5 taps");
+    if (d->ntaps > PARROT_DEBUG_MAX_TAPS) return fail(PARROT_E_UNSUPPORTED, who + ": more than 5 taps");
     if (d->bias1.p && !d->bias0.p) return fail(PARROT_E_INVALID, who + ": bias1 without bias0");
     for (int j = 0; j < d->ntaps; ++j) {
         TRY(reach_ok(Reach().dim(d->M, d->a_sm).dim(d->K, d->a_sk), d->A[j], who, "A"));
@@ -388,7 +389,7 @@ extern "C" int parrot_debug_wgrad(const parrot_debug_wgrad_desc* d, void* ws, si
     const std::string who = "debug_wgrad";
     if (!d || !ws) return fail(PARROT_E_INVALID, who + ": null argument");
     if (d->ntaps < 1 || d->M < 1 || d->K < 1 || d->T < 1 || d->R < 1) return fail(PARROT_E_INVALID, who + ": ntaps, M, K, T and R must be positive");
-    if (d->ntaps > AT_MAX_TAPS) return fail(PARROT_E_UNSUPPORTED, who + ": more than 5 taps");
+    if (d->ntaps > PARROT_DEBUG_MAX_TAPS) return fail(PARROT_E_UNSUPPORTED, who + ": more than 5 taps");
     if (d->R % d->T) return fail(PARROT_E_INVALID, who + ": R must be a multiple of T");
     const int B = d->R / d->T;
     TRY(reach_ok(Reach().dim(B, d->y_sz).dim(d->M, d->y_sm).dim(d->T, d->y_st), d->dY, who, "dY"));

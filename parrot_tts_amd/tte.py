@@ -4,7 +4,8 @@ Same constructor ``Parrot(data_config, src_vocab_size, src_pad_idx)`` (reads
 ``<root_path>/speakers.json`` like the reference, parrot.py:24-26), same ``state_dict`` keys
 (SURVEY 8b), same ``infer(batch) -> List[List[int]]`` / ``forward(batch, inference=True)``, and the teacher-forced
 ``forward(batch)`` (caller durations and target mask, parrot.py:90-110) of an eval-mode model.  The module only holds
-parameters; the arithmetic runs in the HIP library.  Training (a forward in training mode, backward) is out of scope and raises."""
+parameters; the arithmetic runs in the HIP library.  Training (a forward in training mode, backward) is out of scope here and raises:
+it is ``TrainableParrot``'s (tte_train.py)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -368,7 +369,7 @@ class Parrot(RangeFallbackModule):
             return (r["logits"], batch["src_mask"], r["tgt_mask"], r["log_dur"])
         if self.training:
             raise NotImplementedError("parrot_tts_amd.Parrot has no training forward (no backward, dropout or optimiser); call .eval() for "
-                                      "the teacher-forced forward")
+                                      "the teacher-forced forward, or train a parrot_tts_amd.tte_train.TrainableParrot")
         assert "duration" in batch.keys()  # reference modules/parrot.py:92
         r = self._run(batch, want_logits=True, durations=batch["duration"], key_mask=batch["tgt_mask"])
         return (r["logits"], batch["src_mask"], batch["tgt_mask"], r["log_dur"])
