@@ -684,6 +684,58 @@ int parrot_gan_loss(const parrot_gan_term_t* terms, int32_t K, const double* wei
                     double* term_out /* device, K, nullable */, float* total /* device, 1, nullable */, void* ws, size_t ws_bytes,
                     void* stream);
 
+/* ---- training the vocoder's generator (utils/vocoder/models.py:69-169 with weight norm attached; train.py:131-168) ----
+ * CodeGenerator.forward and its full backward as two stateless calls shaped like the TTE's.  Every parameter is read from the DEVICE
+ * pointer given here, in torch's layout, through strides: nothing is packed, cached or copied to the host, neither call synchronises,
+ * and a parameter an optimiser has just updated in place is seen by the next call.
+ *   forward (models.py:153-169, :95-111): x = dict[code] transposed to (B, E, U), with spkr[spkr] broadcast over the frames below it
+ *   when multispkr (model_in_dim == embedding_dim (1 + multispkr): conditioning features are not trainable here) -> conv_pre ->
+ *   per stage: leaky ReLU 0.1, ConvTranspose1d(C, C / 2, k, u, padding (k - u) / 2) by output phase, the n_kernels ResBlock1 / ResBlock2
+ *   (:31-38, :58-62) and ((r0 + r1) + r2) / n_kernels -> leaky ReLU 0.01 (:107) -> conv_post -> tanh.  code (B, U) i64, spkr (B) i64
+ *   (NULL without multispkr), wav (B, 1, parrot_voc_train_out_len(cfg, U)) f32.  An id outside its table gives NaN, never an access.
+ *   Weight norm (models.py:75-91, old style, dim 0): a layer with g runs on w = v (g / ||v||), the norm per row of dim 0 -- the INPUT
+ *   channels of a ConvTranspose1d -- summed in fp64 in a fixed order and rounded once; a layer with g == NULL runs on v as it is
+ *   (remove_weight_norm(), :113-119).  A zero row gives what torch._weight_norm gives: nothing is clamped.
+ *   saved (parrot_voc_train_saved_bytes; NULL = keep nothing, for a forward without a backward) keeps the embedded input, every
+ *   conv's activated input a = lrelu(x), the waveform, and every layer's norms and folded weight.  The leaky ReLU's backward reads
+ *   its mask from there: a > 0, the same predicate as x > 0, so x == 0 takes the slope as in torch.
+ * backward: the gradient of every parameter named in `grads` from grad_wav (B, 1, T).  With s = sum(dw v) in fp64 per row:
+ *   dg = s / ||v||, dv = (g / ||v||) dw - (g s / ||v||^3) v; a layer without g gets dw in `v`.  d dict and d spkr are fixed-order fp64
+ *   row scatters (ascending (b, t)).
+ * All products are exact fp32 (fp32 MFMA, fp32 accumulation); every sum that ends in one number is fp64 in a fixed order.  No
+ * floating-point atomics: two calls on the same inputs agree bit for bit, and a batch row's waveform does not depend on the rows
+ * beside it.  NaN / inf propagate.  Limits (PARROT_E_INVALID, before any HIP call): positive sizes, U >= 1, B <= 65535, odd resblock
+ * kernels and upsample kernels of at most 11 taps with rate <= kernel, every activation below 2^30 elements, and
+ * ceil(B T / 256) x taps <= 65535 for every weight gradient. */
+#define PARROT_VOC_TRAIN_MAX_RB (PARROT_MAX_STAGES * PARROT_MAX_KERNELS * 2 * PARROT_MAX_DIL)
+typedef struct {
+    float* v;    /* weight_v, or the plain weight when g == NULL: (C_out, C_in, k), a ConvTranspose1d's (C_in, C_out, k) */
+    float* g;    /* weight_g (dim 0 rows), nullable */
+    float* bias;
+} parrot_voc_layer_ptrs;
+/* DEVICE pointers of every parameter (the forward and the backward read them) or of every gradient (the backward writes them; a
+ * null field is not wanted and is not computed).  rb is indexed as parrot_voc_weights.rb_w. */
+typedef struct {
+    float* dict;  /* (num_embeddings, embedding_dim) */
+    float* spkr;  /* (n_spkr, embedding_dim), NULL without multispkr */
+    parrot_voc_layer_ptrs conv_pre;
+    parrot_voc_layer_ptrs ups[PARROT_MAX_STAGES];
+    parrot_voc_layer_ptrs rb[PARROT_VOC_TRAIN_MAX_RB];
+    parrot_voc_layer_ptrs conv_post;
+} parrot_voc_train_ptrs;
+/* Samples per row for U units: the ConvTranspose1d length chain (models.py:80-83); 0 beyond the limits. */
+int64_t parrot_voc_train_out_len(const parrot_voc_cfg* cfg, int32_t U);
+/* Bytes of what the forward keeps for the backward, and of the workspace of either call (0 beyond the limits). */
+size_t parrot_voc_train_saved_bytes(const parrot_voc_cfg* cfg, int32_t B, int32_t U);
+size_t parrot_voc_train_workspace_bytes(const parrot_voc_cfg* cfg, int32_t B, int32_t U);
+/* models.py:153-169 (train.py:131: y_g_hat = generator(**x)) */
+int parrot_voc_train_forward(const parrot_voc_cfg* cfg, const parrot_voc_train_ptrs* w, const int64_t* code, const int64_t* spkr, int32_t B,
+                             int32_t U, float* wav, void* saved, void* ws, size_t ws_bytes, void* stream);
+/* the backward of that graph (train.py:166: loss_gen_all.backward()) */
+int parrot_voc_train_backward(const parrot_voc_cfg* cfg, const parrot_voc_train_ptrs* w, const int64_t* code, const int64_t* spkr,
+                              const void* saved, const float* grad_wav, int32_t B, int32_t U, const parrot_voc_train_ptrs* grads, void* ws,
+                              size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -197,6 +197,36 @@ int parrot_debug_tte_embed_grad(const int64_t* ids, const float* dx, float* dtab
 size_t parrot_debug_tte_conv_dw_workspace_bytes(int32_t cout, int32_t cin, int32_t kk, int32_t B, int32_t T, int32_t group);
 int parrot_debug_tte_conv_dw(const float* dY, const float* X, float* dW, int32_t cout, int32_t cin, int32_t kk, int32_t pad, int32_t B, int32_t T,
                              int32_t group, void* ws, size_t ws_bytes, void* stream);
+/* Tests: the leaky-ReLU sites of parrot_voc_train_forward / _backward, numbered in the reference's execution order: per stage the one
+ * before ups[i], then per resblock and dilation the one before convs1[m] and the one before convs2[m] (ResBlock2: the one before
+ * convs[m]); last the one before conv_post.  5 + 5 x 3 x 6 + 1 = 96 for the shipped config.
+ *   lrelu_sites       their number (0 beyond the limits)
+ *   lrelu_site_elems  the elements B C T of site `site` (0 beyond the limits)
+ *   lrelu_mask        out_u8[i] = 1 where the backward passes the gradient through (x > 0), 0 where it multiplies by the slope, read
+ *                     from the `saved` buffer of a forward at (cfg, B, U): the counterpart of parrot_tte_train_dropout_mask. */
+int32_t parrot_voc_train_lrelu_sites(const parrot_voc_cfg* cfg);
+int64_t parrot_voc_train_lrelu_site_elems(const parrot_voc_cfg* cfg, int32_t B, int32_t U, int32_t site);
+int parrot_voc_train_lrelu_mask(const parrot_voc_cfg* cfg, int32_t B, int32_t U, const void* saved, int32_t site, uint8_t* out_u8, void* stream);
+/* Tests: the pieces of the vocoder's training alone (csrc/voc_train.h and the launches host_voc_train.hip makes of tap_gemm_kernel /
+ * wgrad_kernel), on caller-owned dense DEVICE buffers whose sizes follow from the dimensions given.  A conv is described by
+ * (c_in, c_out, k, dil, u, transposed): transposed == 0 is Conv1d(c_in, c_out, k, dilation = dil, padding = dil (k - 1) / 2) with
+ * w (c_out, c_in, k) and T_out = T_in (u must be 1); transposed != 0 is ConvTranspose1d(c_in, c_out, k, u, padding = (k - u) / 2)
+ * with w (c_in, c_out, k) and T_out = (T_in - 1) u - 2 ((k - u) / 2) + k (dil must be 1).
+ *   conv_fwd   y (B, c_out, T_out) = conv(x (B, c_in, T_in)) + bias (nullable)
+ *   conv_dx    dx (B, c_in, T_in) from dy (B, c_out, T_out)
+ *   conv_dw    dw (w's shape) from dy and x; ws: parrot_debug_voc_conv_dw_workspace_bytes (0 for sizes that are not valid)
+ *   wn_fwd     w (rows, len) = v (g / ||v||), norm (rows);  wn_bwd: dv (rows, len), dg (rows) from dw (either nullable)
+ * A null argument, a size below 1, k > 11, an even k of a Conv1d, u > k: PARROT_E_INVALID, before any launch. */
+int parrot_debug_voc_conv_fwd(const float* x, const float* w, const float* bias, float* y, int32_t B, int32_t c_in, int32_t c_out, int32_t k,
+                              int32_t dil, int32_t u, int32_t transposed, int32_t T_in, void* stream);
+int parrot_debug_voc_conv_dx(const float* dy, const float* w, float* dx, int32_t B, int32_t c_in, int32_t c_out, int32_t k, int32_t dil, int32_t u,
+                             int32_t transposed, int32_t T_in, void* stream);
+size_t parrot_debug_voc_conv_dw_workspace_bytes(int32_t B, int32_t c_in, int32_t c_out, int32_t k, int32_t T_in);
+int parrot_debug_voc_conv_dw(const float* dy, const float* x, float* dw, int32_t B, int32_t c_in, int32_t c_out, int32_t k, int32_t dil, int32_t u,
+                             int32_t transposed, int32_t T_in, void* ws, size_t ws_bytes, void* stream);
+int parrot_debug_voc_wn_fwd(const float* v, const float* g, float* w, float* norm, int32_t rows, int32_t len, void* stream);
+int parrot_debug_voc_wn_bwd(const float* dw, const float* v, const float* g, const float* norm, float* dv, float* dg, int32_t rows, int32_t len,
+                            void* stream);
 
 #ifdef __cplusplus
 }

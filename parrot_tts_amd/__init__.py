@@ -1,0 +1,6 @@
+def __getattr__(name):
+    # (resolved on first use: importing the package itself loads neither torch nor the HIP library)
+    if name == "TrainableCodeGenerator":
+        from .vocoder_train import TrainableCodeGenerator
+        return TrainableCodeGenerator
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -104,6 +104,18 @@ class TteDevPtrs(C.Structure):  # parrot_tte_dev_weights / parrot_tte_grads: the
     _fields_ = [(n, C.c_void_p) for n in TTE_TOP_FIELDS] + [("enc", FftDevPtrs * TTE_TRAIN_MAX_LAYERS), ("dec", FftDevPtrs * TTE_TRAIN_MAX_LAYERS)]
 
 
+VOC_TRAIN_MAX_RB = MAX_STAGES * MAX_KERNELS * 2 * MAX_DIL  # PARROT_VOC_TRAIN_MAX_RB of include/parrot_hip.h
+
+
+class VocLayerPtrs(C.Structure):  # parrot_voc_layer_ptrs: DEVICE pointers of one weight-normed layer (g null: a plain weight in v)
+    _fields_ = [("v", C.c_void_p), ("g", C.c_void_p), ("bias", C.c_void_p)]
+
+
+class VocTrainPtrs(C.Structure):  # parrot_voc_train_ptrs: the parameters, or where the backward writes their gradients
+    _fields_ = [("dict", C.c_void_p), ("spkr", C.c_void_p), ("conv_pre", VocLayerPtrs), ("ups", VocLayerPtrs * MAX_STAGES),
+                ("rb", VocLayerPtrs * VOC_TRAIN_MAX_RB), ("conv_post", VocLayerPtrs)]
+
+
 class GanTerm(C.Structure):  # parrot_gan_term_t: 48 bytes
     _fields_ = [("a", C.c_void_p), ("b", C.c_void_p), ("grad_a", C.c_void_p), ("grad_b", C.c_void_p), ("n", C.c_int64),
                 ("op", C.c_int32), ("reserved", C.c_int32)]
@@ -261,6 +273,21 @@ SIGNATURES = {
     "parrot_debug_tte_embed_grad": (C.c_int, [vp, vp, vp, C.c_int64, i32, i32, i32, i32, vp]),
     "parrot_debug_tte_conv_dw_workspace_bytes": (sz, [i32, i32, i32, i32, i32, i32]),
     "parrot_debug_tte_conv_dw": (C.c_int, [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, sz, vp]),
+    "parrot_voc_train_out_len": (C.c_int64, [C.POINTER(VocCfg), i32]),
+    "parrot_voc_train_saved_bytes": (sz, [C.POINTER(VocCfg), i32, i32]),
+    "parrot_voc_train_workspace_bytes": (sz, [C.POINTER(VocCfg), i32, i32]),
+    "parrot_voc_train_forward": (C.c_int, [C.POINTER(VocCfg), C.POINTER(VocTrainPtrs), vp, vp, i32, i32, vp, vp, vp, sz, vp]),
+    "parrot_voc_train_backward": (C.c_int, [C.POINTER(VocCfg), C.POINTER(VocTrainPtrs), vp, vp, vp, vp, i32, i32, C.POINTER(VocTrainPtrs), vp,
+                                            sz, vp]),
+    "parrot_voc_train_lrelu_sites": (i32, [C.POINTER(VocCfg)]),
+    "parrot_voc_train_lrelu_site_elems": (C.c_int64, [C.POINTER(VocCfg), i32, i32, i32]),
+    "parrot_voc_train_lrelu_mask": (C.c_int, [C.POINTER(VocCfg), i32, i32, vp, i32, vp, vp]),
+    "parrot_debug_voc_conv_fwd": (C.c_int, [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp]),
+    "parrot_debug_voc_conv_dx": (C.c_int, [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp]),
+    "parrot_debug_voc_conv_dw_workspace_bytes": (sz, [i32, i32, i32, i32, i32]),
+    "parrot_debug_voc_conv_dw": (C.c_int, [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, sz, vp]),
+    "parrot_debug_voc_wn_fwd": (C.c_int, [vp, vp, vp, vp, i32, i32, vp]),
+    "parrot_debug_voc_wn_bwd": (C.c_int, [vp, vp, vp, vp, vp, vp, i32, i32, vp]),
     "parrot_debug_tap_gemm": (C.c_int, [C.POINTER(DebugTapGemmDesc), vp]),
     "parrot_debug_wgrad_workspace_bytes": (sz, [i32, i32, i32, i32]),
     "parrot_debug_wgrad": (C.c_int, [C.POINTER(DebugWgradDesc), vp, sz, vp]),

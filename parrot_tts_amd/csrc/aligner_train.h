@@ -20,13 +20,17 @@
 
 namespace parrot {
 
-constexpr int AT_MAX_TAPS = 9;     // the widest conv that goes through tap_gemm_kernel: the TTE's k = 9 FFN conv (the aligner's have 5)
+constexpr int AT_MAX_TAPS = 11;    // the widest conv that goes through tap_gemm_kernel: the vocoder's k = 11 (the TTE's FFN has 9, the aligner 5)
 constexpr int AT_RCHUNK = 256;    // (b, t) pairs per weight-gradient / column-sum partial: the fixed block of the two-level sums
 constexpr int AT_ACC_FLUSH = 8;   // tap_gemm_kernel moves its accumulator into a second one every 8 x 32 products
 constexpr int AT_BT = 16;         // batch rows per pass of the LSTM step kernels: their sums live in registers, nothing is staged in LDS
 constexpr int AT_UNITS = 4;       // hidden units per workgroup of the LSTM step kernels (as LSTM_UNITS)
 
 // Y[z][m][n] = act(sum_j sum_k A_j[m][k] X[z][k][n + shift_j] + bias0[m] + bias1[m]); X is zero outside 0 <= n + shift_j < N.
+// The fields after `relu` serve the vocoder's training (voc_train.h); zero in each of them is the line above, bit for bit:
+//   X is read at column n x_mul + shift_j and is zero outside [0, x_n)  (x_mul = 0: 1; x_n = 0: N): a transposed conv's phases and its
+//   data gradient;  then, after the bias:  v = mask[z][m][n] > 0 ? v : v mslope  (a leaky ReLU's backward on its saved output),
+//   v += res[z][m][n]  (a residual), both at C's strides;  and after `relu`:  v = v > 0 ? v : v lslope  when lrelu.
 struct TapGemmParams {
     const float* A[AT_MAX_TAPS];  // tap j: A_j[m][k] at A[j] + m a_sm + k a_sk
     long x_off[AT_MAX_TAPS];      // tap j reads X[z] + x_off[j] (a column block of a wider array)
@@ -39,9 +43,17 @@ struct TapGemmParams {
     const float* bias0;           // nullable; bias1 (nullable) is added to bias0 first, in fp32 (b_ih + b_hh)
     const float* bias1;
     int relu;
+    int x_mul, x_n;
+    const float* mask;
+    float mslope;
+    const float* res;
+    int lrelu;
+    float lslope;
 };
 // part[chunk][j][m][k] = sum over the chunk's (b, t) of dY[b][m][t] X[b][k][t + shift_j]; chunk c covers r = b T + t in
 // [c AT_RCHUNK, (c + 1) AT_RCHUNK).  X is zero outside 0 <= t + shift_j < T.
+// x_mul, x_T (zero: 1 and T, the line above): X is read at t x_mul + shift_j and is zero outside [0, x_T): the weight gradient of a
+// transposed conv, whose input is in dY's role and whose output gradient, u times as long, in X's.
 struct WgradParams {
     const float* dY;  // dY[b][m][t] at dY + b y_sz + m y_sm + t y_st
     const float* X;   // X[b][k][t] at X + b x_sz + k x_sk + t x_st
@@ -49,6 +61,7 @@ struct WgradParams {
     int M, K, T, R, ntaps;
     int shift[AT_MAX_TAPS];
     long y_sz, y_sm, y_st, x_sz, x_sk, x_st;
+    int x_mul, x_T;
 };
 struct BnTrainParams {
     const float* x;   // (B, C, T): the ReLU's output
@@ -124,6 +137,7 @@ __global__ __launch_bounds__(256) void tap_gemm_kernel(const TapGemmParams p) {
     for (int r = 0; r < 16; ++r) acc[r] = tot[r] = 0.f;
     int since = 0;
     const bool a_kfast = (p.a_sk == 1), x_kfast = (p.x_sn != 1);
+    const int x_mul = p.x_mul ? p.x_mul : 1, x_n = p.x_n ? p.x_n : p.N;
     for (int j = 0; j < p.ntaps; ++j) {
         const float* __restrict__ A = p.A[j];
         const float* __restrict__ Xj = X + p.x_off[j];
@@ -139,9 +153,9 @@ __global__ __launch_bounds__(256) void tap_gemm_kernel(const TapGemmParams p) {
                 As[kk][mm] = v;
                 int kb, nn;
                 if (x_kfast) { nn = idx / KC; kb = idx % KC; } else { kb = idx / 64; nn = idx % 64; }
-                const int tn = n0 + nn + sh;
+                const int tn = (n0 + nn) * x_mul + sh;
                 float w = 0.f;
-                if (k0 + kb < p.K && n0 + nn < p.N && tn >= 0 && tn < p.N) w = Xj[(long)(k0 + kb) * p.x_sk + (long)tn * p.x_sn];
+                if (k0 + kb < p.K && n0 + nn < p.N && tn >= 0 && tn < x_n) w = Xj[(long)(k0 + kb) * p.x_sk + (long)tn * p.x_sn];
                 Bs[kb][nn] = w;
             }
             __syncthreads();
@@ -170,8 +184,16 @@ __global__ __launch_bounds__(256) void tap_gemm_kernel(const TapGemmParams p) {
         if (m < p.M && n < p.N) {
             float v = tot[r] + acc[r];
             if (p.bias0) v += p.bias1 ? __fadd_rn(p.bias0[m], p.bias1[m]) : p.bias0[m];
+            const long o = (long)m * p.c_sm + (long)n * p.c_sn;
+            if (p.mask || p.res) {
+#pragma clang fp contract(off)  // (the product and the sum are rounded one after the other, as torch rounds them)
+                const long oz = (long)blockIdx.z * p.c_sz + o;
+                if (p.mask && !(p.mask[oz] > 0.f)) v = v * p.mslope;
+                if (p.res) v = v + p.res[oz];
+            }
             if (p.relu) v = v < 0.f ? 0.f : v;  // (a NaN stays a NaN, as torch's relu keeps it)
-            C[(long)m * p.c_sm + (long)n * p.c_sn] = v;
+            if (p.lrelu) v = v > 0.f ? v : v * p.lslope;
+            C[o] = v;
         }
     }
 }
@@ -195,6 +217,7 @@ __global__ __launch_bounds__(256) void wgrad_kernel(const WgradParams p) {
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[r] = 0.f;
     const bool y_rfast = (p.y_st == 1), x_rfast = (p.x_st == 1);
+    const int x_mul = p.x_mul ? p.x_mul : 1, x_T = p.x_T ? p.x_T : p.T;
     for (int r0 = r_lo; r0 < r_hi; r0 += KC) {
 #pragma unroll
         for (int i = 0; i < (KC * 64) / 256; ++i) {
@@ -211,8 +234,8 @@ __global__ __launch_bounds__(256) void wgrad_kernel(const WgradParams p) {
             if (x_rfast) { nn = idx / KC; kb = idx % KC; } else { kb = idx / 64; nn = idx % 64; }
             float w = 0.f;
             if (r0 + kb < r_hi && n0 + nn < p.K) {
-                const int b = (r0 + kb) / p.T, t = (r0 + kb) - b * p.T + sh;
-                if (t >= 0 && t < p.T) w = p.X[(long)b * p.x_sz + (long)(n0 + nn) * p.x_sk + (long)t * p.x_st];
+                const int b = (r0 + kb) / p.T, t = ((r0 + kb) - b * p.T) * x_mul + sh;
+                if (t >= 0 && t < x_T) w = p.X[(long)b * p.x_sz + (long)(n0 + nn) * p.x_sk + (long)t * p.x_st];
             }
             Bs[kb][nn] = w;
         }

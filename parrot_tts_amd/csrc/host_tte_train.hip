@@ -16,6 +16,8 @@ using namespace parrot;
 namespace {
 
 constexpr int ML = PARROT_TTE_TRAIN_MAX_LAYERS;
+constexpr int TTE_MAX_TAPS = 9;  // the FFN's widest kernel here (tap_gemm_kernel itself takes AT_MAX_TAPS)
+static_assert(TTE_MAX_TAPS <= AT_MAX_TAPS, "one slot per tap");
 // The weight-gradient partials (chunks x taps x M x K floats, chunks = ceil(B T / 256)) are formed for as many taps at a time as fit
 // in WG_BUDGET bytes, and always for at least one: the buffer is at most max(64 MiB, chunks x the largest single-tap M x K x 4 bytes).
 constexpr size_t WG_BUDGET = (size_t)64 << 20;
@@ -125,11 +127,11 @@ bool cfg_quiet_ok(const parrot_tte_train_cfg* c, int B, int S, int L) {
     if (t.d_model < 1 || t.n_filter_ffn < 1 || t.dp_filter < 1 || t.vocab < 1 || t.n_codes < 1 || t.max_len < 1) return false;
     if (t.enc_layers < 0 || t.dec_layers < 0 || t.enc_layers > ML || t.dec_layers > ML) return false;
     if (t.enc_heads < 1 || t.dec_heads < 1 || t.d_model % t.enc_heads || t.d_model % t.dec_heads) return false;
-    if (t.ffn_k1 < 1 || t.ffn_k2 < 1 || !(t.ffn_k1 & 1) || !(t.ffn_k2 & 1) || t.ffn_k1 > AT_MAX_TAPS || t.ffn_k2 > AT_MAX_TAPS || t.dp_kernel != 3) return false;
+    if (t.ffn_k1 < 1 || t.ffn_k2 < 1 || !(t.ffn_k1 & 1) || !(t.ffn_k2 & 1) || t.ffn_k1 > TTE_MAX_TAPS || t.ffn_k2 > TTE_MAX_TAPS || t.dp_kernel != 3) return false;
     if (!(c->p_enc >= 0.f && c->p_enc <= 1.f && c->p_dec >= 0.f && c->p_dec <= 1.f && c->p_dp >= 0.f && c->p_dp <= 1.f)) return false;
     if (B < 1 || S < 1 || L < 1) return false;
     const long Tm = std::max(S, L), H = std::max(t.enc_heads, t.dec_heads);
-    if ((long)B * H > 65535 || (long)B * Tm > 0x3fffffffL || (long)wgrad_chunks((int)(B * Tm)) * AT_MAX_TAPS > 65535) return false;
+    if ((long)B * H > 65535 || (long)B * Tm > 0x3fffffffL || (long)wgrad_chunks((int)(B * Tm)) * TTE_MAX_TAPS > 65535) return false;
     return true;
 }
 int cfg_ok(const parrot_tte_train_cfg* c, int B, int S, int L, const std::string& who) {
@@ -523,7 +525,7 @@ extern "C" int parrot_debug_tte_embed_grad(const int64_t* ids, const float* dx, 
 }
 namespace {
 bool conv_dw_sizes_ok(int cout, int cin, int kk, int pad, int B, int T, int group) {
-    return cout >= 1 && cin >= 1 && kk >= 1 && kk <= AT_MAX_TAPS && pad >= 0 && pad < kk && B >= 1 && T >= 1 && (long)B * T <= 0x3fffffffL && group >= 1 &&
+    return cout >= 1 && cin >= 1 && kk >= 1 && kk <= TTE_MAX_TAPS && pad >= 0 && pad < kk && B >= 1 && T >= 1 && (long)B * T <= 0x3fffffffL && group >= 1 &&
            group <= kk && (long)wgrad_chunks(B * T) * group <= 65535;
 }
 }  // namespace

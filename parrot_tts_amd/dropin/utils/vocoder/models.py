@@ -1,2 +1,3 @@
 from parrot_tts_amd.gan_loss import discriminator_loss, feature_loss, generator_loss  # noqa: F401
 from parrot_tts_amd.vocoder import CodeGenerator  # noqa: F401
+from parrot_tts_amd.vocoder_train import TrainableCodeGenerator  # noqa: F401
