@@ -92,7 +92,7 @@ int parrot_debug_argmax_guard(const float* logits, int32_t B, int32_t V, int32_t
 /* Stage taps of the aligner: while set, every parrot_aligner_forward copies the activation after the third BatchNorm, channel-first
  * (B, conv_dim, T), to bn3_dev and the LSTM output (B, T, 2 lstm_dim) to lstm_dev (DEVICE buffers; NULL entries are skipped). */
 int parrot_aligner_debug_stages(parrot_aligner_t*, float* bn3_dev, float* lstm_dev);
-/* Tests: the aligner's training kernels (csrc/aligner_train.h) on their own, through the launch code of parrot_aligner_train_forward /
+/* Tests: the aligner's training kernels (csrc/train_gemm.h, csrc/aligner_train.h) on their own, through the launch code of parrot_aligner_train_forward /
  * _backward (csrc/host_aligner_train.hip), on caller-owned DEVICE buffers.  Each descriptor mirrors the kernel's parameter struct;
  * every buffer it names is a parrot_debug_buf: the pointer and the number of floats behind it.  Before any launch the entry point
  * computes on the host the smallest and largest element index the strides, offsets, shifts and sizes can reach in every buffer:

@@ -1,6 +1,6 @@
 // host_aligner_train.hip -- training the forced aligner: the batch-statistics forward and the full backward as two stateless calls
-// (kernels and launchers: aligner_train.h / tu_aligner_train.hip).  No handle, no packed weights, no host copy and no
-// synchronisation: every weight is read from the device pointer it is given.
+// (kernels and launchers: aligner_train.h / tu_aligner_train.hip; the matrix products: train_gemm_host.h).  No handle, no packed
+// weights, no host copy and no synchronisation: every weight is read from the device pointer it is given.
 #include "host_common.h"
 
 #include <algorithm>
@@ -8,13 +8,14 @@
 
 #include "aligner.h"
 #include "aligner_train.h"
+#include "train_gemm_host.h"
 
 using namespace parrot;
 
 namespace {
 
 constexpr int ALIGNER_TAPS = 5;  // the aligner's convs; also the slots of the debug descriptors
-constexpr long AT_MAX_BT = (long)(65535 / ALIGNER_TAPS) * AT_RCHUNK;  // wgrad_kernel's grid.z = chunks x taps
+constexpr long AT_MAX_BT = (long)(65535 / ALIGNER_TAPS) * TG_RCHUNK;  // wgrad_kernel's grid.z = chunks x taps: every weight gradient is one launch
 
 // What the forward keeps for the backward.  Activations are channel-first (B, C, T) around the convs, (B, T, C) around the LSTM.
 struct TrainSaved {
@@ -50,7 +51,8 @@ struct TrainScratch {
     float *dlstm, *dgates; // (B, T, 2H), (B, T, 8H)
     float *dc, *w_hh_t;    // [2][B][H], [2][H][4H]
     float *da, *db;        // (B, conv_dim, T) each: gradient at a block's output / at its conv's output
-    float* part;           // chunks x the largest weight gradient
+    float* part;           // chunks x the largest weight gradient, all its taps: with B T <= AT_MAX_BT wgrad_group never splits one
+    size_t part_floats;
     double* colpart;       // chunks x max(8H, V)
 };
 TrainScratch train_scratch(const parrot_aligner_cfg& cfg, Arena& ar, int B, int T) {
@@ -68,7 +70,8 @@ TrainScratch train_scratch(const parrot_aligner_cfg& cfg, Arena& ar, int B, int 
     w.da = ar.take<float>(BT * D);
     w.db = ar.take<float>(BT * D);
     size_t wmax = std::max(std::max(D * D * 5, D * F * 5), std::max(std::max(4 * H * D, 4 * H * H), V * 2 * H));
-    w.part = ar.take<float>(chunks * wmax);
+    w.part_floats = chunks * wmax;
+    w.part = ar.take<float>(w.part_floats);
     w.colpart = ar.take<double>(chunks * std::max(8 * H, V));
     return w;
 }
@@ -93,26 +96,6 @@ int weights_ok(const parrot_aligner_dev_weights* w, const char* who) {
     return ok ? PARROT_OK : fail(PARROT_E_INVALID, std::string(who) + ": null weight");
 }
 
-// one-tap GEMM Y[z] (M x N) = A (M x K) X[z] (K x N): the shape of every 1 x 1 product here
-TapGemmParams gemm1(const float* A, long a_sm, long a_sk, const float* X, long x_sz, long x_sk, long x_sn, float* C, long c_sz, long c_sm, long c_sn,
-                    int M, int N, int K) {
-    TapGemmParams g{};
-    g.ntaps = 1;
-    g.A[0] = A;
-    g.X = X; g.C = C;
-    g.M = M; g.N = N; g.K = K;
-    g.a_sm = a_sm; g.a_sk = a_sk;
-    g.x_sz = x_sz; g.x_sk = x_sk; g.x_sn = x_sn;
-    g.c_sz = c_sz; g.c_sm = c_sm; g.c_sn = c_sn;
-    return g;
-}
-// dA_j = sum_(b, t) dY X^T: partials, then the fp64 sum in chunk order into out[m o_sm + k o_sk + j o_sj]
-int wgrad(WgradParams q, float* part, float* out, long o_sm, long o_sk, long o_sj, hipStream_t s) {
-    q.part = part;
-    HIP_TRY(launch_wgrad(q, s));
-    HIP_TRY(launch_wgrad_reduce(part, wgrad_chunks(q.R), q.ntaps, q.M, q.K, out, o_sm, o_sk, o_sj, s));
-    return PARROT_OK;
-}
 // The training recurrence as the forward runs it: lstm_run_steps (host_aligner.hip) over lstm_train_step_kernel.  The initial state
 // into half 0 of hbuf [2][2][B][H] and into q.c (zeros when h0 / c0 are null), one launch per step; afterwards h of the last step is
 // half n_steps & 1 of hbuf and c is q.c.  Also behind parrot_debug_lstm.
@@ -165,20 +148,10 @@ extern "C" int parrot_aligner_train_forward(const parrot_aligner_cfg* cfg, const
     const TrainSaved sv = train_saved(*cfg, sa, B, T);
     // 3 x [conv(k = 5, pad 2) -> ReLU -> BatchNorm] on the padded batch as it stands (model.py:16-19, 41-45)
     for (int i = 0; i < 3; ++i) {
-        const int cin = i ? D : F;
-        TapGemmParams g{};
-        g.ntaps = 5;
-        for (int j = 0; j < 5; ++j) {
-            g.A[j] = wt->conv_w[i] + j;  // (conv_dim, cin, 5)
-            g.shift[j] = j - 2;
-        }
-        g.a_sm = (long)cin * 5; g.a_sk = 5;
-        if (i == 0) { g.X = mel; g.x_sz = (long)T * F; g.x_sk = 1; g.x_sn = F; }  // mel (B, T, n_mels) read transposed
-        else { g.X = sv.y[i - 1]; g.x_sz = (long)D * T; g.x_sk = T; g.x_sn = 1; }
-        g.C = sv.r[i]; g.c_sz = (long)D * T; g.c_sm = T; g.c_sn = 1;
-        g.M = D; g.N = T; g.K = cin;
-        g.relu = 1;
-        HIP_TRY(launch_tap_gemm(g, B, s));
+        Epi relu;
+        relu.relu = 1;
+        const Lay lx = i ? chan_first(D, T) : chan_last(T, F);  // mel (B, T, n_mels) read transposed
+        TRY(conv_fwd(ConvW{wt->conv_w[i], D, i ? D : F, 5, 1, 2}, i ? sv.y[i - 1] : mel, lx, sv.r[i], chan_first(D, T), B, T, relu, s));
         BnTrainParams bn{};
         bn.x = sv.r[i]; bn.y = sv.y[i];
         bn.gamma = wt->bn_weight[i]; bn.beta = wt->bn_bias[i];
@@ -190,20 +163,18 @@ extern "C" int parrot_aligner_train_forward(const parrot_aligner_cfg* cfg, const
     }
     // W_ih x + (b_ih + b_hh) of both directions for all frames, written as (B, T, 8H)
     for (int d = 0; d < 2; ++d) {
-        TapGemmParams g = gemm1(wt->w_ih[d], D, 1, sv.y[2], (long)D * T, T, 1, w.xproj + (size_t)d * 4 * H, (long)T * 8 * H, 1, 8 * H, 4 * H, T, D);
-        g.bias0 = wt->b_ih[d];
-        g.bias1 = wt->b_hh[d];
-        HIP_TRY(launch_tap_gemm(g, B, s));
+        Epi bias;
+        bias.bias0 = wt->b_ih[d]; bias.bias1 = wt->b_hh[d];
+        TRY(conv_fwd(ConvW{wt->w_ih[d], 4 * H, D, 1, 1, 0}, sv.y[2], chan_first(D, T), w.xproj + (size_t)d * 4 * H, chan_last(T, 8 * H), B, T, bias, s));
     }
     LstmTrainParams q{};
     q.w_hh[0] = wt->w_hh[0]; q.w_hh[1] = wt->w_hh[1];
     q.xproj = w.xproj; q.c = w.cbuf; q.out = sv.h; q.gates = sv.gates; q.c_all = sv.c_all;
     q.B = B; q.T = T; q.H = H;
     TRY(lstm_train_run_steps(q, w.hbuf, nullptr, nullptr, T, s));  // h_0 = c_0 = 0
-    TapGemmParams g = gemm1(wt->lin_w, 2 * H, 1, sv.h, (long)T * 2 * H, 1, 2 * H, logits, (long)T * V, 1, V, V, T, 2 * H);
-    g.bias0 = wt->lin_b;
-    HIP_TRY(launch_tap_gemm(g, B, s));
-    return PARROT_OK;
+    Epi bias;
+    bias.bias0 = wt->lin_b;
+    return conv_fwd(ConvW{wt->lin_w, V, 2 * H, 1, 1, 0}, sv.h, chan_last(T, 2 * H), logits, chan_last(T, V), B, T, bias, s);
 }
 
 extern "C" int parrot_aligner_train_backward(const parrot_aligner_cfg* cfg, const parrot_aligner_dev_weights* wt, const float* mel, const void* saved,
@@ -236,19 +207,13 @@ extern "C" int parrot_aligner_train_backward(const parrot_aligner_cfg* cfg, cons
     }
     Arena sa(const_cast<void*>(saved), saved_bytes(*cfg, B, T));
     const TrainSaved sv = train_saved(*cfg, sa, B, T);
-    const long T2 = (long)T * 2 * H, T8 = (long)T * 8 * H, DT = (long)D * T;
+    const Lay lh = chan_last(T, 2 * H), lg = chan_last(T, 8 * H), lv = chan_last(T, V), lc = chan_first(D, T);  // h / dlstm, gates, logits, conv blocks
+    const ConvW lin{wt->lin_w, V, 2 * H, 1, 1, 0};
 
     // ---- Linear(2H -> V): db, dW, dX -------------------------------------------------------------
-    if (gr->lin_b) HIP_TRY(launch_colsum(grad_logits, BT, V, V, w.colpart, gr->lin_b, nullptr, s));
-    if (gr->lin_w) {
-        WgradParams q{};
-        q.dY = grad_logits; q.y_sz = (long)T * V; q.y_sm = 1; q.y_st = V;
-        q.X = sv.h; q.x_sz = T2; q.x_sk = 1; q.x_st = 2 * H;
-        q.M = V; q.K = 2 * H; q.T = T; q.R = BT; q.ntaps = 1;
-        TRY(wgrad(q, w.part, gr->lin_w, 2 * H, 1, 0, s));
-    }
-    // dlstm (B, T, 2H) = grad_logits lin_w: A = lin_w^T through its strides
-    HIP_TRY(launch_tap_gemm(gemm1(wt->lin_w, 1, 2 * H, grad_logits, (long)T * V, 1, V, w.dlstm, T2, 1, 2 * H, 2 * H, T, V), B, s));
+    if (gr->lin_b) TRY(colsum(grad_logits, BT, V, V, w.colpart, gr->lin_b, nullptr, s));
+    if (gr->lin_w) TRY(conv_dw(lin, grad_logits, lv, sv.h, lh, gr->lin_w, B, T, w.part, w.part_floats, s));
+    TRY(conv_dx(lin, grad_logits, lv, w.dlstm, lh, B, T, Epi(), s));  // dlstm (B, T, 2H) = grad_logits lin_w
 
     // ---- the LSTM back through time, both directions per launch ----------------------------------
     for (int d = 0; d < 2; ++d) HIP_TRY(launch_align_transpose(wt->w_hh[d], w.w_hh_t + (size_t)d * H * 4 * H, 1, 4 * H, H, s));
@@ -263,25 +228,21 @@ extern "C" int parrot_aligner_train_backward(const parrot_aligner_cfg* cfg, cons
     for (int d = 0; d < 2; ++d) {
         const float* dg = w.dgates + (size_t)d * 4 * H;
         if (gr->b_ih[d] || gr->b_hh[d])  // db_ih = db_hh = sum dgates: one sum, written twice
-            HIP_TRY(launch_colsum(dg, BT, 4 * H, 8 * H, w.colpart, gr->b_ih[d] ? gr->b_ih[d] : gr->b_hh[d], gr->b_ih[d] ? gr->b_hh[d] : nullptr, s));
-        WgradParams q{};
-        q.dY = dg; q.y_sz = T8; q.y_sm = 1; q.y_st = 8 * H;
-        q.M = 4 * H; q.T = T; q.R = BT; q.ntaps = 1;
-        if (gr->w_ih[d]) {
-            q.X = sv.y[2]; q.x_sz = DT; q.x_sk = T; q.x_st = 1; q.K = D;
-            TRY(wgrad(q, w.part, gr->w_ih[d], D, 1, 0, s));
-        }
-        if (gr->w_hh[d]) {  // dW_hh = sum_t dgates_t^T h at the step before t: t - 1 forward, t + 1 backward; the zero fill is h_0 = 0
-            q.X = sv.h + (size_t)d * H; q.x_sz = T2; q.x_sk = 1; q.x_st = 2 * H; q.K = H;
-            q.shift[0] = d ? 1 : -1;
-            TRY(wgrad(q, w.part, gr->w_hh[d], H, 1, 0, s));
-        }
+            TRY(colsum(dg, BT, 4 * H, 8 * H, w.colpart, gr->b_ih[d] ? gr->b_ih[d] : gr->b_hh[d], gr->b_ih[d] ? gr->b_hh[d] : nullptr, s));
+        if (gr->w_ih[d]) TRY(conv_dw(ConvW{nullptr, 4 * H, D, 1, 1, 0}, dg, lg, sv.y[2], lc, gr->w_ih[d], B, T, w.part, w.part_floats, s));
+        // dW_hh = sum_t dgates_t^T h at the step before t: one tap at t - 1 forward (pad 1), t + 1 backward (pad -1); the zero fill is h_0 = 0
+        if (gr->w_hh[d]) TRY(conv_dw(ConvW{nullptr, 4 * H, H, 1, 1, d ? -1 : 1}, dg, lg, sv.h + (size_t)d * H, lh, gr->w_hh[d], B, T, w.part, w.part_floats, s));
     }
-    {   // dy_2 (B, conv_dim, T) = W_ih^T dgates + W_ih_reverse^T dgates_reverse: two taps without a shift
-        TapGemmParams g = gemm1(wt->w_ih[0], 1, D, w.dgates, T8, 1, 8 * H, w.da, DT, T, 1, D, T, 4 * H);
+    {   // dy_2 (B, conv_dim, T) = W_ih^T dgates + W_ih_reverse^T dgates_reverse: two taps without a shift.  (A raw struct: two weights
+        // and a per-tap column offset into X are no conv, and nobody else wants them.)
+        TapGemmParams g{};
         g.ntaps = 2;
-        g.A[1] = wt->w_ih[1];
+        g.A[0] = wt->w_ih[0]; g.A[1] = wt->w_ih[1];
         g.x_off[1] = 4 * H;
+        g.a_sm = 1; g.a_sk = D;
+        g.X = w.dgates; g.x_sz = lg.sz; g.x_sk = lg.sc; g.x_sn = lg.st;
+        g.C = w.da; g.c_sz = lc.sz; g.c_sm = lc.sc; g.c_sn = lc.st;
+        g.M = D; g.N = T; g.K = 4 * H;
         HIP_TRY(launch_tap_gemm(g, B, s));
     }
     // ---- the conv blocks, last to first: BatchNorm + ReLU backward, conv weight gradient, conv data gradient -----
@@ -293,38 +254,21 @@ extern "C" int parrot_aligner_train_backward(const parrot_aligner_cfg* cfg, cons
         bb.dgamma = gr->bn_weight[i]; bb.dbeta = gr->bn_bias[i];
         bb.B = B; bb.C = D; bb.T = T;
         HIP_TRY(launch_bn_relu_bwd(bb, s));
-        if (gr->conv_w[i]) {
-            WgradParams q{};
-            q.dY = w.db; q.y_sz = DT; q.y_sm = T; q.y_st = 1;
-            if (i == 0) { q.X = mel; q.x_sz = (long)T * F; q.x_sk = 1; q.x_st = F; }
-            else { q.X = sv.y[i - 1]; q.x_sz = DT; q.x_sk = T; q.x_st = 1; }
-            q.M = D; q.K = cin; q.T = T; q.R = BT; q.ntaps = 5;
-            for (int j = 0; j < 5; ++j) q.shift[j] = j - 2;
-            TRY(wgrad(q, w.part, gr->conv_w[i], (long)cin * 5, 5, 1, s));
-        }
+        const ConvW cw{wt->conv_w[i], D, cin, 5, 1, 2};
+        if (gr->conv_w[i]) TRY(conv_dw(cw, w.db, lc, i ? sv.y[i - 1] : mel, i ? lc : chan_last(T, F), gr->conv_w[i], B, T, w.part, w.part_floats, s));
         if (i == 0) break;  // mel gets no gradient
-        TapGemmParams g{};  // dy_{i-1}[k][t] = sum_j sum_m w[m][k][j] dconv[m][t - (j - 2)]
-        g.ntaps = 5;
-        for (int j = 0; j < 5; ++j) {
-            g.A[j] = wt->conv_w[i] + j;
-            g.shift[j] = 2 - j;
-        }
-        g.a_sm = 5; g.a_sk = (long)D * 5;
-        g.X = w.db; g.x_sz = DT; g.x_sk = T; g.x_sn = 1;
-        g.C = w.da; g.c_sz = DT; g.c_sm = T; g.c_sn = 1;
-        g.M = D; g.N = T; g.K = D;
-        HIP_TRY(launch_tap_gemm(g, B, s));
+        TRY(conv_dx(cw, w.db, lc, w.da, lc, B, T, Epi(), s));
     }
     return PARROT_OK;
 }
 
 // ---------------------------------------------------------------------------------------------
-// Debug entry points (include/parrot_hip_debug.h): the kernels above on caller-owned buffers, through gemm1 / wgrad() / the
-// launch_* helpers.  Nothing is launched before every index the descriptor can reach has been bounded on the host.
+// Debug entry points (include/parrot_hip_debug.h): the kernels above on caller-owned buffers, through wgrad_taps() / the launch_*
+// helpers; the descriptors mirror the kernels' own parameter structs, so they are filled field by field.  Nothing is launched before every index the descriptor can reach has been bounded on the host.
 // ---------------------------------------------------------------------------------------------
 namespace {
 
-static_assert(PARROT_DEBUG_MAX_TAPS == ALIGNER_TAPS && ALIGNER_TAPS <= AT_MAX_TAPS, "the debug descriptors hold one slot per tap");
+static_assert(PARROT_DEBUG_MAX_TAPS == ALIGNER_TAPS && ALIGNER_TAPS <= TG_MAX_TAPS, "the debug descriptors hold one slot per tap");
 
 // smallest and largest element index of sum_i idx_i stride_i + offset, idx_i in [lo_i, hi_i]
 struct Reach {
@@ -369,7 +313,11 @@ extern "C" int parrot_debug_tap_gemm(const parrot_debug_tap_gemm_desc* d, void* 
     TRY(reach_ok(Reach().dim(d->Z, d->c_sz).dim(d->M, d->c_sm).dim(d->N, d->c_sn), d->C, who, "C"));
     if (d->bias0.p) TRY(reach_ok(Reach().dim(d->M, 1), d->bias0, who, "bias0"));
     if (d->bias1.p) TRY(reach_ok(Reach().dim(d->M, 1), d->bias1, who, "bias1"));
-    TapGemmParams g = gemm1(d->A[0].p, d->a_sm, d->a_sk, d->X.p, d->x_sz, d->x_sk, d->x_sn, d->C.p, d->c_sz, d->c_sm, d->c_sn, d->M, d->N, d->K);
+    TapGemmParams g{};
+    g.X = d->X.p; g.x_sz = d->x_sz; g.x_sk = d->x_sk; g.x_sn = d->x_sn;
+    g.C = d->C.p; g.c_sz = d->c_sz; g.c_sm = d->c_sm; g.c_sn = d->c_sn;
+    g.a_sm = d->a_sm; g.a_sk = d->a_sk;
+    g.M = d->M; g.N = d->N; g.K = d->K;
     g.ntaps = d->ntaps;
     for (int j = 0; j < d->ntaps; ++j) {
         g.A[j] = d->A[j].p;
@@ -407,9 +355,8 @@ extern "C" int parrot_debug_wgrad(const parrot_debug_wgrad_desc* d, void* ws, si
     WgradParams q{};
     q.dY = d->dY.p; q.y_sz = d->y_sz; q.y_sm = d->y_sm; q.y_st = d->y_st;
     q.X = d->X.p; q.x_sz = d->x_sz; q.x_sk = d->x_sk; q.x_st = d->x_st;
-    q.M = d->M; q.K = d->K; q.T = d->T; q.R = d->R; q.ntaps = d->ntaps;
-    for (int j = 0; j < d->ntaps; ++j) q.shift[j] = d->shift[j];
-    return wgrad(q, (float*)ws, d->out.p, d->o_sm, d->o_sk, d->o_sj, s);
+    q.M = d->M; q.K = d->K; q.T = d->T; q.R = d->R;
+    return wgrad_taps(q, d->shift, d->ntaps, d->out.p, d->o_sm, d->o_sk, d->o_sj, (float*)ws, ws_bytes / sizeof(float), s);  // (one group: checked above)
 }
 
 extern "C" size_t parrot_debug_colsum_workspace_bytes(int32_t R, int32_t M) {

@@ -1,5 +1,5 @@
 // host_tte_train.hip -- training the text-to-unit model: the teacher-forced forward with dropout and the full backward as two
-// stateless calls (kernels: tte_train.h / tu_tte_train.hip; the matrix products: aligner_train.h, attn.h).  No handle, no packed
+// stateless calls (kernels: tte_train.h / tu_tte_train.hip; the matrix products: train_gemm_host.h, attn.h).  No handle, no packed
 // weights, no host copy and no synchronisation: every weight is read from the device pointer it is given, in torch's layout.
 // Activations are channel-last (B, T, C) throughout, so a Linear is one tap_gemm over all B T rows and a conv one per batch row.
 #include "host_common.h"
@@ -8,7 +8,7 @@
 #include <cmath>
 #include <string>
 
-#include "aligner_train.h"
+#include "train_gemm_host.h"
 #include "tte_train.h"
 
 using namespace parrot;
@@ -16,11 +16,8 @@ using namespace parrot;
 namespace {
 
 constexpr int ML = PARROT_TTE_TRAIN_MAX_LAYERS;
-constexpr int TTE_MAX_TAPS = 9;  // the FFN's widest kernel here (tap_gemm_kernel itself takes AT_MAX_TAPS)
-static_assert(TTE_MAX_TAPS <= AT_MAX_TAPS, "one slot per tap");
-// The weight-gradient partials (chunks x taps x M x K floats, chunks = ceil(B T / 256)) are formed for as many taps at a time as fit
-// in WG_BUDGET bytes, and always for at least one: the buffer is at most max(64 MiB, chunks x the largest single-tap M x K x 4 bytes).
-constexpr size_t WG_BUDGET = (size_t)64 << 20;
+constexpr int TTE_MAX_TAPS = 9;  // the FFN's widest kernel here (tap_gemm_kernel itself takes TG_MAX_TAPS)
+static_assert(TTE_MAX_TAPS <= TG_MAX_TAPS, "one slot per tap");
 
 struct Dims {
     int B, S, L, D, F, K1, K2, NF, DK, V, vocab, nspk, He, Hd, Le, Ld, Tm;
@@ -73,12 +70,11 @@ size_t saved_bytes(const Dims& d) {
     (void)saved_layout(ar, d);
     return align_up(ar.off, 256);
 }
-size_t part_per_chunk(const Dims& d) {  // floats of weight-gradient partials per chunk
+size_t part_floats_for(const Dims& d) {  // the weight-gradient partials of the largest layer, every layer sized for B Tm rows
     const size_t D = d.D, F = d.F, NF = d.NF;
-    const size_t one = std::max({3 * D * D, F * D, NF * D, NF * NF, (size_t)d.V * D});
-    const size_t all = std::max({3 * D * D, F * D * d.K1, D * F * d.K2, NF * D * d.DK, NF * NF * d.DK, (size_t)d.V * D});
-    const size_t chunks = (size_t)wgrad_chunks(d.B * d.Tm);
-    return std::max(one, std::min(all, WG_BUDGET / sizeof(float) / chunks));
+    const int R = d.B * d.Tm;
+    return std::max({wgrad_part_floats(R, 3 * D * D, 1), wgrad_part_floats(R, F * D, d.K1), wgrad_part_floats(R, D * F, d.K2),
+                     wgrad_part_floats(R, NF * D, d.DK), wgrad_part_floats(R, NF * NF, d.DK), wgrad_part_floats(R, (size_t)d.V * D, 1)});
 }
 // One workspace layout for both calls.  pd, t0 and ld_raw serve every call; after them the region of an eval forward's `saved` (used
 // only when the caller keeps nothing: training = 0, saved = NULL) and the backward's own buffers share the same bytes -- no call uses
@@ -111,7 +107,7 @@ Scratch scratch_layout(Arena& ar, const Dims& d) {
     w.dP = ar.take<float>(R * H * d.Tm);
     w.zl = ar.take<float>((size_t)d.B * d.L * d.V);
     w.zd = ar.take<float>((size_t)d.B * d.S);
-    w.part_floats = chunks * part_per_chunk(d);
+    w.part_floats = part_floats_for(d);
     w.part = ar.take<float>(w.part_floats);
     w.colpart = ar.take<double>(chunks * std::max({3 * D, (size_t)d.F, (size_t)d.NF, (size_t)d.V}));
     if (ar.off < eval_end) {
@@ -153,75 +149,35 @@ int weights_ok(const parrot_tte_train_cfg* c, const parrot_tte_dev_weights* w, c
     return ok ? PARROT_OK : fail(PARROT_E_INVALID, who + ": null weight");
 }
 
-// ---- the matrix products, by shape -----------------------------------------------------------------------------------------
+// ---- the matrix products, by shape (train_gemm_host.h, channel-last; a Linear: one batch row of all B T rows) -----------------
 // Y (rows, out; row stride ldy) = X (rows, in; ldx) W^T + bias, W (out, in)
 int lin(const float* W, const float* X, long ldx, float* Y, long ldy, int out, int in, long rows, const float* bias, hipStream_t s) {
-    TapGemmParams g{};
-    g.ntaps = 1; g.A[0] = W; g.a_sm = in; g.a_sk = 1;
-    g.X = X; g.x_sk = 1; g.x_sn = ldx;
-    g.C = Y; g.c_sm = 1; g.c_sn = ldy;
-    g.M = out; g.N = (int)rows; g.K = in;
-    g.bias0 = bias;
-    HIP_TRY(launch_tap_gemm(g, 1, s));
-    return PARROT_OK;
+    Epi e;
+    e.bias0 = bias;
+    return conv_fwd(ConvW{W, out, in, 1, 1, 0}, X, chan_last((int)rows, ldx), Y, chan_last((int)rows, ldy), 1, (int)rows, e, s);
 }
 // dX (rows, in; ldx) = dY (rows, out; ldy) W
 int lin_dx(const float* W, const float* dY, long ldy, float* dX, long ldx, int out, int in, long rows, hipStream_t s) {
-    TapGemmParams g{};
-    g.ntaps = 1; g.A[0] = W; g.a_sm = 1; g.a_sk = in;
-    g.X = dY; g.x_sk = 1; g.x_sn = ldy;
-    g.C = dX; g.c_sm = 1; g.c_sn = ldx;
-    g.M = in; g.N = (int)rows; g.K = out;
-    HIP_TRY(launch_tap_gemm(g, 1, s));
-    return PARROT_OK;
+    return conv_dx(ConvW{W, out, in, 1, 1, 0}, dY, chan_last((int)rows, ldy), dX, chan_last((int)rows, ldx), 1, (int)rows, Epi(), s);
 }
 // dW[m][k][j] = sum_(b, t) dY[b][t][m] X[b][t + j - pad][k], taps in groups that fit the partial buffer; kk = 1, B = 1: a Linear
 int conv_dw(const float* dY, long ldy, const float* X, long ldx, float* dW, int cout, int cin, int kk, int pad, int B, int T, const Scratch& w,
             hipStream_t s) {
     if (!dW) return PARROT_OK;
-    const int R = B * T, chunks = wgrad_chunks(R);
-    int G = (int)std::min<size_t>((size_t)kk, w.part_floats / ((size_t)chunks * cout * cin));
-    G = std::max(1, std::min(G, 65535 / chunks));
-    for (int j0 = 0; j0 < kk; j0 += G) {
-        WgradParams q{};
-        q.dY = dY; q.y_sz = (long)T * ldy; q.y_sm = 1; q.y_st = ldy;
-        q.X = X; q.x_sz = (long)T * ldx; q.x_sk = 1; q.x_st = ldx;
-        q.M = cout; q.K = cin; q.T = T; q.R = R; q.ntaps = std::min(G, kk - j0);
-        for (int j = 0; j < q.ntaps; ++j) q.shift[j] = j0 + j - pad;
-        q.part = w.part;
-        HIP_TRY(launch_wgrad(q, s));
-        HIP_TRY(launch_wgrad_reduce(w.part, chunks, q.ntaps, cout, cin, dW + j0, (long)cin * kk, kk, 1, s));
-    }
-    return PARROT_OK;
+    return parrot::conv_dw(ConvW{nullptr, cout, cin, kk, 1, pad}, dY, chan_last(T, ldy), X, chan_last(T, ldx), dW, B, T, w.part, w.part_floats, s);
 }
 // Y (B, T, cout) = act(conv1d(X (B, T, cin), W (cout, cin, kk), padding = pad) + bias)
 int conv(const float* W, const float* bias, const float* X, float* Y, int cout, int cin, int kk, int pad, int B, int T, int relu, hipStream_t s) {
-    TapGemmParams g{};
-    g.ntaps = kk;
-    for (int j = 0; j < kk; ++j) { g.A[j] = W + j; g.shift[j] = j - pad; }
-    g.a_sm = (long)cin * kk; g.a_sk = kk;
-    g.X = X; g.x_sz = (long)T * cin; g.x_sk = 1; g.x_sn = cin;
-    g.C = Y; g.c_sz = (long)T * cout; g.c_sm = 1; g.c_sn = cout;
-    g.M = cout; g.N = T; g.K = cin;
-    g.bias0 = bias; g.relu = relu;
-    HIP_TRY(launch_tap_gemm(g, B, s));
-    return PARROT_OK;
+    Epi e;
+    e.bias0 = bias; e.relu = relu;
+    return conv_fwd(ConvW{W, cout, cin, kk, 1, pad}, X, chan_last(T, cin), Y, chan_last(T, cout), B, T, e, s);
 }
 // dX[b][t][k] = sum_j sum_m W[m][k][j] dY[b][t - (j - pad)][m]
 int conv_dx(const float* W, const float* dY, float* dX, int cout, int cin, int kk, int pad, int B, int T, hipStream_t s) {
-    TapGemmParams g{};
-    g.ntaps = kk;
-    for (int j = 0; j < kk; ++j) { g.A[j] = W + j; g.shift[j] = pad - j; }
-    g.a_sm = kk; g.a_sk = (long)cin * kk;
-    g.X = dY; g.x_sz = (long)T * cout; g.x_sk = 1; g.x_sn = cout;
-    g.C = dX; g.c_sz = (long)T * cin; g.c_sm = 1; g.c_sn = cin;
-    g.M = cin; g.N = T; g.K = cout;
-    HIP_TRY(launch_tap_gemm(g, B, s));
-    return PARROT_OK;
+    return parrot::conv_dx(ConvW{W, cout, cin, kk, 1, pad}, dY, chan_last(T, cout), dX, chan_last(T, cin), B, T, Epi(), s);
 }
 int colsum(const float* src, long rows, int M, float* out, const Scratch& w, hipStream_t s) {
-    if (out) HIP_TRY(launch_colsum(src, (int)rows, M, M, w.colpart, out, nullptr, s));
-    return PARROT_OK;
+    return out ? parrot::colsum(src, rows, M, M, w.colpart, out, nullptr, s) : PARROT_OK;
 }
 // the attention's batched products: operand (b, h) of an array of row stride ld lies at b T ld + h hd; of P at (b H + h) T T
 BgemmTrainParams bg(const float* A, long a_sk, long a_sm, long a_zb, long a_zh, const float* Bm, long b_sk, long b_sn, long b_zb, long b_zh, float* C,

@@ -1,5 +1,5 @@
 // host_voc_train.hip -- training the vocoder's generator: CodeGenerator.forward with weight norm attached and its full backward as
-// two stateless calls (kernels: voc_train.h / tu_voc_train.hip; the matrix products: aligner_train.h).  No handle, no packed weights,
+// two stateless calls (kernels: voc_train.h / tu_voc_train.hip; the matrix products: train_gemm_host.h).  No handle, no packed weights,
 // no host copy and no synchronisation: every parameter is read from the device pointer it is given, in torch's layout.  Activations
 // are channel-first (B, C, T) throughout, so a conv is one tap_gemm per batch row (grid z = B) and a transposed conv one per phase.
 #include "host_common.h"
@@ -8,8 +8,8 @@
 #include <string>
 #include <vector>
 
-#include "aligner_train.h"
-#include "tte_train.h"  // (tt_launch_embed_grad: the fixed-order fp64 row scatter)
+#include "train_gemm_host.h"
+#include "tte_train.h"  // (borrowed: tt_launch_embed_grad alone, the fixed-order fp64 row scatter of both tables' gradients)
 #include "voc_train.h"
 
 using namespace parrot;
@@ -17,15 +17,15 @@ using namespace parrot;
 namespace {
 
 constexpr float SLOPE = 0.1f, SLOPE_POST = 0.01f;  // LRELU_SLOPE (models.py:10) and F.leaky_relu's default (models.py:107)
-constexpr int MAX_K = AT_MAX_TAPS;
-// The weight-gradient partials (chunks x taps x M x K floats, chunks = ceil(B T / 256)) are formed for as many taps at a time as fit
-// in WG_BUDGET bytes, and always for at least one.
-constexpr size_t WG_BUDGET = (size_t)64 << 20;
+constexpr int MAX_K = TG_MAX_TAPS;
 
 struct LayerDesc {
     int cin, cout, k, dil, u, transposed;
     int Tin, Tout;
     int rows() const { return transposed ? cin : cout; }  // dim 0 of the weight
+    ConvW conv(const float* W) const { return ConvW{W, cout, cin, k, dil, (k - 1) / 2 * dil}; }  // (not transposed: padding dil (k - 1) / 2)
+    Lay in() const { return chan_first(cin, Tin); }
+    Lay out() const { return chan_first(cout, Tout); }
     size_t len() const { return (size_t)(transposed ? cout : cin) * k; }
     size_t wsize() const { return (size_t)cin * cout * k; }
 };
@@ -69,7 +69,7 @@ bool cfg_quiet_ok(const parrot_voc_cfg* c, long B, long U) {
             if (dl < 1 || dl * k > lim) return false;
         }
     }
-    if ((B * T + AT_RCHUNK - 1) / AT_RCHUNK * maxk > 65535) return false;
+    if ((B * T + TG_RCHUNK - 1) / TG_RCHUNK * maxk > 65535) return false;
     return true;
 }
 int cfg_ok(const parrot_voc_cfg* c, int B, int U, const std::string& who) {
@@ -161,11 +161,7 @@ std::vector<Site> sites(const Saved& sv, const Dims& d) {
 
 size_t part_floats_for(const Dims& d) {
     size_t need = 0;
-    for (const LayerDesc& l : d.L) {
-        const size_t chunks = (size_t)wgrad_chunks(d.B * l.Tin), one = (size_t)l.cin * l.cout;
-        const size_t all = one * l.k, fit = WG_BUDGET / sizeof(float) / chunks;
-        need = std::max(need, chunks * std::max(one, std::min(all, fit)));
-    }
+    for (const LayerDesc& l : d.L) need = std::max(need, wgrad_part_floats(d.B * l.Tin, (size_t)l.cin * l.cout, l.k));
     return need;
 }
 // The forward's workspace: conv_pre's output, the stage's running x, one buffer per resblock of the stage, conv_post's output, and
@@ -205,71 +201,32 @@ size_t workspace_bytes(const Dims& d) {
     return align_up(std::max(a.off, b.off), 256);
 }
 
-// ---- the matrix products, by shape -------------------------------------------------------------------------------------------
-struct Epi {  // what tap_gemm_kernel's epilogue does beyond the bias
-    const float* mask = nullptr;
-    float mslope = 0.f;
-    const float* res = nullptr;
-    int lrelu = 0;
-    float lslope = 0.f;
-};
-void set_epi(TapGemmParams& g, const Epi& e) {
-    g.mask = e.mask; g.mslope = e.mslope; g.res = e.res; g.lrelu = e.lrelu; g.lslope = e.lslope;
-}
+// ---- the matrix products, by shape (train_gemm_host.h, channel-first) -------------------------------------------------------
 // Y (B, cout, T) = conv1d(X (B, cin, T), W (cout, cin, k), dilation dil, padding dil (k - 1) / 2) + bias: tap j has shift (j - (k - 1) / 2) dil
-int conv_fwd(const LayerDesc& l, const float* W, const float* bias, const float* X, float* Y, int B, const Epi& e, hipStream_t s) {
-    TapGemmParams g{};
-    g.ntaps = l.k;
-    for (int j = 0; j < l.k; ++j) { g.A[j] = W + j; g.shift[j] = (j - (l.k - 1) / 2) * l.dil; }
-    g.a_sm = (long)l.cin * l.k; g.a_sk = l.k;
-    g.X = X; g.x_sz = (long)l.cin * l.Tin; g.x_sk = l.Tin; g.x_sn = 1;
-    g.C = Y; g.c_sz = (long)l.cout * l.Tin; g.c_sm = l.Tin; g.c_sn = 1;
-    g.M = l.cout; g.N = l.Tin; g.K = l.cin;
-    g.bias0 = bias;
-    set_epi(g, e);
-    HIP_TRY(launch_tap_gemm(g, B, s));
-    return PARROT_OK;
+int conv_fwd(const LayerDesc& l, const float* W, const float* bias, const float* X, float* Y, int B, Epi e, hipStream_t s) {
+    e.bias0 = bias;
+    return parrot::conv_fwd(l.conv(W), X, l.in(), Y, l.out(), B, l.Tin, e, s);
 }
-// dX[b][ci][t] = sum_j sum_co W[co][ci][j] dY[b][co][t - shift_j]: the same launch with A transposed through its strides and the
-// shifts negated.  Rows [ci0, ci0 + nci) of dX only, written at (c_sz, c_sm, c_sn): the embedding gradients want (B, U, E).
-int conv_dx(const LayerDesc& l, const float* W, const float* dY, float* dX, int B, const Epi& e, hipStream_t s, int ci0 = 0, int nci = -1,
-            long c_sz = 0, long c_sm = 0, long c_sn = 0) {
+// dX[b][ci][t] = sum_j sum_co W[co][ci][j] dY[b][co][t - shift_j]
+int conv_dx(const LayerDesc& l, const float* W, const float* dY, float* dX, int B, const Epi& e, hipStream_t s) {
+    return parrot::conv_dx(l.conv(W), dY, l.out(), dX, l.in(), B, l.Tin, e, s);
+}
+// Rows [ci0, ci0 + E) of conv_pre's data gradient, written as (B, U, E) for tt_launch_embed_grad.  (A raw struct: a sub-range of
+// the weight's input channels is no ConvW, and nobody else wants one.)
+int conv_pre_dx_rows(const LayerDesc& l, const float* W, const float* dY, float* dX, int B, int ci0, int E, hipStream_t s) {
     TapGemmParams g{};
     g.ntaps = l.k;
     for (int j = 0; j < l.k; ++j) { g.A[j] = W + (size_t)ci0 * l.k + j; g.shift[j] = -(j - (l.k - 1) / 2) * l.dil; }
     g.a_sm = l.k; g.a_sk = (long)l.cin * l.k;
     g.X = dY; g.x_sz = (long)l.cout * l.Tin; g.x_sk = l.Tin; g.x_sn = 1;
-    g.C = dX;
-    if (nci < 0) { g.c_sz = (long)l.cin * l.Tin; g.c_sm = l.Tin; g.c_sn = 1; nci = l.cin; }
-    else { g.c_sz = c_sz; g.c_sm = c_sm; g.c_sn = c_sn; }
-    g.M = nci; g.N = l.Tin; g.K = l.cout;
-    set_epi(g, e);
+    g.C = dX; g.c_sz = (long)l.Tin * E; g.c_sm = 1; g.c_sn = E;
+    g.M = E; g.N = l.Tin; g.K = l.cout;
     HIP_TRY(launch_tap_gemm(g, B, s));
-    return PARROT_OK;
-}
-// the partials of `nt` taps and their fixed-order reduction into dW + j0 (torch layout: row stride row_len k, column stride k, tap 1)
-int wgrad_groups(WgradParams q, const int* shifts, int k, int M, int K, float* dW, float* part, size_t part_floats, hipStream_t s) {
-    const int chunks = wgrad_chunks(q.R);
-    int G = (int)std::min<size_t>((size_t)k, part_floats / ((size_t)chunks * M * K));
-    G = std::max(1, std::min(G, 65535 / chunks));
-    for (int j0 = 0; j0 < k; j0 += G) {
-        q.ntaps = std::min(G, k - j0);
-        for (int j = 0; j < q.ntaps; ++j) q.shift[j] = shifts[j0 + j];
-        q.part = part;
-        HIP_TRY(launch_wgrad(q, s));
-        HIP_TRY(launch_wgrad_reduce(part, chunks, q.ntaps, M, K, dW + j0, (long)K * k, k, 1, s));
-    }
     return PARROT_OK;
 }
 // dW[co][ci][j] = sum_(b, t) dY[b][co][t] X[b][ci][t + shift_j]
 int conv_dw(const LayerDesc& l, const float* dY, const float* X, float* dW, int B, float* part, size_t part_floats, hipStream_t s) {
-    WgradParams q{};
-    q.dY = dY; q.y_sz = (long)l.cout * l.Tin; q.y_sm = l.Tin; q.y_st = 1;
-    q.X = X; q.x_sz = (long)l.cin * l.Tin; q.x_sk = l.Tin; q.x_st = 1;
-    q.M = l.cout; q.K = l.cin; q.T = l.Tin; q.R = B * l.Tin;
-    int shifts[MAX_K];
-    for (int j = 0; j < l.k; ++j) shifts[j] = (j - (l.k - 1) / 2) * l.dil;
-    return wgrad_groups(q, shifts, l.k, l.cout, l.cin, dW, part, part_floats, s);
+    return parrot::conv_dw(l.conv(nullptr), dY, l.out(), X, l.in(), dW, B, l.Tin, part, part_floats, s);
 }
 // ConvTranspose1d(cin, cout, k, u, padding p = (k - u) / 2), W (cin, cout, k), by output phase: sample n u + r is a conv over the taps
 // j = r + p (mod u) with shift (r + p - j) / u, written with column stride u.  X is bounded by Tin, not by the phase's length.
@@ -316,7 +273,7 @@ int convt_dw(const LayerDesc& l, const float* dY, const float* X, float* dW, int
     q.M = l.cin; q.K = l.cout; q.T = l.Tin; q.R = B * l.Tin;
     int shifts[MAX_K];
     for (int j = 0; j < l.k; ++j) shifts[j] = j - p;
-    return wgrad_groups(q, shifts, l.k, l.cin, l.cout, dW, part, part_floats, s);
+    return wgrad_taps(q, shifts, l.k, dW, (long)l.cout * l.k, l.k, 1, part, part_floats, s);
 }
 
 int ptrs_ok(const Dims& d, const parrot_voc_train_ptrs* w, const std::string& who) {
@@ -497,13 +454,13 @@ extern "C" int parrot_voc_train_backward(const parrot_voc_cfg* cfg, const parrot
     }
     // ---- conv_pre and the two tables: w.gx is the gradient at conv_pre's output ----------------------------------------------
     TRY(layer_grads(d, 0, *wt, *gr, sv, w.gx, sv.emb, w, s));
-    const long E = d.E, RU = (long)B * U;
+    const long RU = (long)B * U;
     if (gr->dict) {
-        TRY(conv_dx(d.L[0], W(0), w.gx, w.gemb, B, Epi(), s, 0, d.E, (long)U * E, 1, E));  // (B, U, E)
+        TRY(conv_pre_dx_rows(d.L[0], W(0), w.gx, w.gemb, B, 0, d.E, s));
         HIP_TRY(tt_launch_embed_grad(code, w.gemb, gr->dict, RU, 1, d.E, d.n_emb, -1, s));
     }
     if (d.multi && gr->spkr) {
-        TRY(conv_dx(d.L[0], W(0), w.gx, w.gemb, B, Epi(), s, d.E, d.E, (long)U * E, 1, E));
+        TRY(conv_pre_dx_rows(d.L[0], W(0), w.gx, w.gemb, B, d.E, d.E, s));
         HIP_TRY(tt_launch_embed_grad(spkr, w.gemb, gr->spkr, RU, U, d.E, d.n_spkr, -1, s));
     }
     return PARROT_OK;
@@ -545,7 +502,7 @@ bool debug_conv_ok(long B, long cin, long cout, long k, long dil, long u, int tr
     const long Tout = transposed ? (Tin - 1) * u - 2 * ((k - u) / 2) + k : Tin;
     const long lim = 0x3fffffffL;
     if (Tout < 1 || B * Tin * cin > lim || B * Tout * cout > lim || dil * k > lim || cin * cout * k > lim) return false;
-    if ((B * Tin + AT_RCHUNK - 1) / AT_RCHUNK * k > 65535) return false;
+    if ((B * Tin + TG_RCHUNK - 1) / TG_RCHUNK * k > 65535) return false;
     *l = LayerDesc{(int)cin, (int)cout, (int)k, (int)dil, (int)u, transposed ? 1 : 0, (int)Tin, (int)Tout};
     return true;
 }

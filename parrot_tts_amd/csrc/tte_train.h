@@ -1,15 +1,15 @@
 // tte_train.h -- the kernels that TRAIN the text-to-unit model (reference modules/parrot.py:90-110 with inference=False under
 // model.train(), and the backward of that graph): parrot_tte_train_forward / _backward (host_tte_train.hip).  Everything is
 // channel-last, (rows, C) with rows = b T + t, as torch holds it.  The matrix products are not here: the Linear layers and the convs
-// go through tap_gemm_kernel / wgrad_kernel / colsum_* (aligner_train.h), QK^T, PV and their five gradient products through
-// bgemm_mfma_kernel (attn.h), all on v_mfma_f32_32x32x2_f32.  This file holds what lies between them:
+// go through train_gemm.h, QK^T, PV and their five gradient products through bgemm_mfma_kernel (attn.h), all on
+// v_mfma_f32_32x32x2_f32.  This file holds what lies between them:
 //   ln_fwd_kernel            LayerNorm over C keeping the row's mean and rstd
 //   ln_bwd_kernel            its data gradient (+ a residual, x an optional ReLU mask) and dy xhat, whose column sums are dgamma
 //   softmax_drop_fwd_kernel  key-masked row softmax P, and P with dropout
 //   softmax_drop_bwd_kernel  dS = P (dP - sum_k dP_k P_k), dP the dropout's backward of the incoming gradient
 //   dropout_kernel           y = keep ? x / (1 - p) : 0 (forward, and backward on the gradient); relu_bwd_kernel; add / mask kernels
 //   tt_embed_kernel, tt_add_speaker_kernel, dur_cum_kernel, lr_fwd_kernel, lr_bwd_kernel, embed_grad_kernel
-// Rules, as in aligner_train.h: no floating-point atomics; every sum over rows that ends in one number is fp64 in a fixed order;
+// Rules, as in train_gemm.h: no floating-point atomics; every sum over rows that ends in one number is fp64 in a fixed order;
 // nothing clamps with fmaxf, so a NaN stays a NaN.
 //
 // DROPOUT BITS.  Element i of dropout site `site` under (seed, offset) is kept iff
@@ -21,6 +21,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include "wave_reduce.h"
 
 namespace parrot {
 
@@ -88,16 +90,6 @@ __device__ __forceinline__ bool drop_keep(const DropArgs& d, uint32_t thr, uint6
                                            (uint32_t)(d.seed >> 32));
     return (w >> 8) >= thr;
 }
-__device__ __forceinline__ float tt_wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-__device__ __forceinline__ double tt_wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
 // max that keeps a NaN (fmaxf would drop it)
 __device__ __forceinline__ float nan_max(float a, float b) { return (b > a || b != b) ? b : a; }
 
@@ -111,13 +103,13 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const float* __restrict__ x
     const float* xr = x + row * C;
     double s = 0.0;
     for (int c = lane; c < C; c += 64) s += (double)xr[c];
-    const double md = tt_wave_sum(s) / (double)C;
+    const double md = wave_sum(s) / (double)C;
     s = 0.0;
     for (int c = lane; c < C; c += 64) {
         const double d = (double)xr[c] - md;
         s += d * d;
     }
-    const float m = (float)md, r = (float)(1.0 / sqrt(tt_wave_sum(s) / (double)C + 1e-5));
+    const float m = (float)md, r = (float)(1.0 / sqrt(wave_sum(s) / (double)C + 1e-5));
     if (lane == 0) {
         mean[row] = m;
         rstd[row] = r;
@@ -141,7 +133,7 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const float* __restrict__ d
         a1 += (double)g;
         a2 += (double)g * (double)xh;
     }
-    const float s1 = (float)(tt_wave_sum(a1) / (double)C), s2 = (float)(tt_wave_sum(a2) / (double)C);
+    const float s1 = (float)(wave_sum(a1) / (double)C), s2 = (float)(wave_sum(a2) / (double)C);
     for (int c = lane; c < C; c += 64) {
         const float xv = xr[c], xh = (xv - m) * r, d = dr[c], g = d * gamma[c];
         float v = r * ((g - s1) - xh * s2);
@@ -170,7 +162,7 @@ __global__ __launch_bounds__(256) void softmax_drop_fwd_kernel(float* __restrict
         sr[t] = e;
         sum += e;
     }
-    sum = tt_wave_sum(sum);
+    sum = wave_sum(sum);
     const uint32_t thr = drop_threshold(d.p);
     const float scale = 1.f / (1.f - d.p);
     for (int t = lane; t < T; t += 64) {
@@ -195,7 +187,7 @@ __global__ __launch_bounds__(256) void softmax_drop_bwd_kernel(const float* __re
         dr[t] = g;
         sum = fmaf(g, pr[t], sum);
     }
-    sum = tt_wave_sum(sum);
+    sum = wave_sum(sum);
     for (int t = lane; t < T; t += 64) dr[t] = pr[t] * (dr[t] - sum);
 }
 

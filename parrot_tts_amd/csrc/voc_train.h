@@ -1,9 +1,8 @@
 // voc_train.h -- the kernels that TRAIN the vocoder's generator (reference utils/vocoder/models.py:69-169 with weight norm attached,
 // and the backward of that graph): parrot_voc_train_forward / _backward (host_voc_train.hip).  Activations are channel-first,
 // (B, C, T), as torch holds them.  The matrix products are not here: every Conv1d, every phase of a ConvTranspose1d, their data
-// gradients and their weight gradients go through tap_gemm_kernel / wgrad_kernel / wgrad_reduce_kernel (aligner_train.h) on
-// v_mfma_f32_32x32x2_f32, with the leaky ReLU's backward, the residual add and the activation of the next conv in tap_gemm_kernel's
-// epilogue.  This file holds what lies between them:
+// gradients and their weight gradients go through train_gemm.h, with the leaky ReLU's backward, the residual add and the activation
+// of the next conv in tap_gemm_kernel's epilogue.  This file holds what lies between them:
 //   vt_wn_fwd_kernel     weight norm, old style, dim 0: w = v (g / ||v||), the norm per row over everything else (fp64, fixed order)
 //   vt_wn_bwd_kernel     dg = s / ||v||, dv = (g / ||v||) dw - (g s / ||v||^3) v with s = sum dw v (fp64, fixed order)
 //   vt_embed_kernel      x (B, E (1 + multispkr), U) = dict[code] transposed, spkr[spkr] broadcast over the frames below it
@@ -11,11 +10,13 @@
 //   vt_mrf_kernel        ((r0 + r1) + r2 ...) / n_kernels, a true division;  vt_div_kernel its backward
 //   vt_tanh_kernel, vt_tanh_bwd_kernel (from the saved output), vt_add_kernel
 //   vt_chansum_kernel    bias gradients: out[c] = sum over (b, t), ascending per thread then a fixed tree, fp64
-// Rules, as in aligner_train.h: no floating-point atomics; every sum that ends in one number is fp64 in a fixed order; nothing clamps
+// Rules, as in train_gemm.h: no floating-point atomics; every sum that ends in one number is fp64 in a fixed order; nothing clamps
 // with fmaxf, so a NaN stays a NaN.  The launchers are defined in tu_voc_train.hip, which alone sees the kernel bodies.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include "wave_reduce.h"
 
 namespace parrot {
 
@@ -39,21 +40,6 @@ hipError_t vt_launch_chansum(const float* g, float* out, int B, int C, int T, hi
 
 #ifdef PARROT_VOC_TRAIN_TU
 
-// fp64 sum over the 256 threads of a workgroup in a fixed tree; every thread gets the result
-__device__ __forceinline__ double vt_block_sum(double v, double* sm) {
-    const int tid = threadIdx.x;
-    sm[tid] = v;
-    __syncthreads();
-#pragma unroll
-    for (int o = 128; o > 0; o >>= 1) {
-        if (tid < o) sm[tid] += sm[tid + o];
-        __syncthreads();
-    }
-    const double r = sm[0];
-    __syncthreads();
-    return r;
-}
-
 // One workgroup per row.  ||v|| = sqrt(sum v^2): thread tid adds elements tid, tid + 256, ... in fp64, then the fixed tree; rounded to
 // fp32 once and kept for the backward.  w = v (g / ||v||), the quotient formed once in fp32 (torch._weight_norm's own order).  A zero
 // row divides by zero as torch does: nothing is clamped.
@@ -64,7 +50,7 @@ __global__ __launch_bounds__(256) void vt_wn_fwd_kernel(const float* __restrict_
     const float* vr = v + (size_t)row * len;
     double s = 0.0;
     for (int i = tid; i < len; i += 256) s += (double)vr[i] * (double)vr[i];
-    const float nf = (float)sqrt(vt_block_sum(s, sm));
+    const float nf = (float)sqrt(block_sum(s, sm));
     if (tid == 0) norm[row] = nf;
     const float ratio = g[row] / nf;
     float* wr = w + (size_t)row * len;
@@ -79,7 +65,7 @@ __global__ __launch_bounds__(256) void vt_wn_bwd_kernel(const float* __restrict_
     const float* dr = dw + (size_t)row * len;
     double s = 0.0;
     for (int i = tid; i < len; i += 256) s += (double)dr[i] * (double)vr[i];
-    s = vt_block_sum(s, sm);
+    s = block_sum(s, sm);
     const double n = (double)norm[row], gg = (double)g[row];
     if (dg && tid == 0) dg[row] = (float)(s / n);
     if (dv) {
@@ -156,7 +142,7 @@ __global__ __launch_bounds__(256) void vt_chansum_kernel(const float* __restrict
         const long b = i / T, t = i - b * T;
         s += (double)g[((size_t)b * C + c) * T + t];
     }
-    s = vt_block_sum(s, sm);
+    s = block_sum(s, sm);
     if (tid == 0) out[c] = (float)s;
 }
 

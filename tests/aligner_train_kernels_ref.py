@@ -1,4 +1,4 @@
-"""Plain numpy restatement of the aligner's training kernels (parrot_tts_amd/csrc/aligner_train.h), one function per kernel, each
+"""Plain numpy restatement of the aligner's training kernels (parrot_tts_amd/csrc/train_gemm.h, aligner_train.h), one function per kernel, each
 evaluating the kernel's documented formula on the strided buffers a descriptor names -- and the descriptors themselves: the
 parameter sets parrot_tts_amd/csrc/host_aligner_train.hip builds, written once as functions of the problem sizes.
 
@@ -13,9 +13,9 @@ import math
 import numpy as np
 
 MAX_TAPS = 5
-RCHUNK = 256     # AT_RCHUNK: (b, t) pairs per fp32 partial of wgrad_kernel
+RCHUNK = 256     # TG_RCHUNK: (b, t) pairs per fp32 partial of wgrad_kernel
 PASS_K = 32      # k per staging pass of tap_gemm_kernel
-ACC_FLUSH = 8    # AT_ACC_FLUSH
+ACC_FLUSH = 8    # TG_ACC_FLUSH
 U32 = 2.0 ** -24
 
 
@@ -23,7 +23,7 @@ U32 = 2.0 ** -24
 # the layouts of host_aligner_train.hip, in the GEMM's own sizes (M x K times K x N, Z batch rows) ...
 # =========================================================================================================================================
 def tg_conv(M, N, K, Z, first: bool, relu=1):
-    """Conv forward, k = 5, pad 2 (host_aligner_train.hip:149-163): weight (M, K, 5), tap j at w + j, shift j - 2; input the mel
+    """Conv forward, k = 5, pad 2 (the conv blocks of parrot_aligner_train_forward, host_aligner_train.hip): weight (M, K, 5), tap j at w + j, shift j - 2; input the mel
     (Z, N, K) read transposed (``first``) or channel-first (Z, K, N); output channel-first (Z, M, N), ReLU."""
     x = dict(x_sz=N * K, x_sk=1, x_sn=K) if first else dict(x_sz=K * N, x_sk=N, x_sn=1)
     return dict(ntaps=5, a_off=list(range(5)), x_off=[0] * 5, shift=[j - 2 for j in range(5)], M=M, N=N, K=K, Z=Z, a_sm=K * 5, a_sk=5,

@@ -81,6 +81,30 @@ def test_length_regulator_workspace_bytes_are_the_recorded_ones(lib):
         assert lib.parrot_length_regulator_workspace_bytes(B, S, D, 33) == 0, (B, S, D)
 
 
+def test_train_workspace_and_saved_bytes_are_the_recorded_ones(lib):
+    """parrot_{aligner,tte,voc}_train_{workspace,saved}_bytes return what they returned before the three training units came to share
+    one set of product wrappers and one weight-gradient partial-buffer rule (tests/golden/train_workspace_bytes.json, recorded by
+    tools/make_workspace_goldens.py --train, which says why these shapes: either side of the 64 MiB budget, and a single-tap
+    group).  Every case carries the config it was recorded with.  Needs no device."""
+    import json
+    from parrot_tts_amd import _lib
+    with open(os.path.join(ROOT, "tests", "golden", "train_workspace_bytes.json")) as f:
+        golden = json.load(f)
+    tup = lambda v: tuple(tup(x) for x in v) if isinstance(v, list) else v
+    make = {"aligner": lambda c: _lib.AlignerCfg(**c),
+            "tte": lambda c: _lib.TteTrainCfg(tte=_lib.TteCfg(**c), pad_idx=0, p_enc=0.1, p_dec=0.1, p_dp=0.5),
+            "voc": lambda c: _lib.VocCfg(**{k: tup(v) for k, v in c.items()})}
+    assert sorted(golden) == sorted(make) and all(len(golden[m]) >= 5 for m in make)
+    for model, cases in golden.items():
+        for case in cases:
+            cfg = make[model](case["cfg"])
+            for what in ("workspace", "saved"):
+                got = getattr(lib, f"parrot_{model}_train_{what}_bytes")(ctypes.byref(cfg), *case["shape"])
+                assert got == case[what], (model, what, case["shape"])
+    assert [c["workspace"] for c in golden["aligner"]].count(0) == 1  # (the one refused shape; every other query answers)
+    assert all(c["workspace"] > 0 and c["saved"] > 0 for m in ("tte", "voc") for c in golden[m])
+
+
 def test_struct_sizes_match_header():
     from parrot_tts_amd import _lib
     assert ctypes.sizeof(_lib.ConvDesc) == 12 * 4

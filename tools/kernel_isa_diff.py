@@ -2,7 +2,7 @@
 """Compare the gfx950 machine code of two builds kernel by kernel:  tools/kernel_isa_diff.py OBJDIR_A OBJDIR_B
 Every *.o of a directory is unbundled to its code object and disassembled.  Kernels are matched on their names without the
 internal-linkage mark (a `static` may come and go; demangled for display where a c++filt exists) and compared instruction by
-instruction, with their VGPR / SGPR / LDS / scratch numbers.  One line per kernel: copies in A, copies in B (units that hold
+instruction (without the s_nop fill behind a kernel's last instruction, which follows its place in the unit), with their VGPR / SGPR / LDS / scratch numbers.  One line per kernel: copies in A, copies in B (units that hold
 it), then SAME / DIFF / ONLY_A / ONLY_B.  SAME means that every copy in B equals SOME copy in A: where A's own copies differ
 (units built with different flags) the line names the units of A whose copy B kept, and it is for the reader to check that
 the launched one is among them.  Exit status 1 unless everything is SAME.  Needs no GPU."""
@@ -65,6 +65,8 @@ def kernels(objdir):
                     body[cur].append(line.split("//")[0].strip())
             names = [s for s in body if s in res]  # kernels only (not device functions kept out of line)
             for s in names:
+                while body[s] and body[s][-1] == "s_nop 0":  # (the fill up to the next function or behind the unit's last one: it
+                    body[s].pop()                            # follows the kernel's place in its unit, not the kernel)
                 out[external_name(s)].append((os.path.basename(obj), body[s], res[s]))
     filt = shutil.which("llvm-cxxfilt", path=LLVM) or shutil.which("c++filt")
     if filt and out:
