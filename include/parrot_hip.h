@@ -736,6 +736,57 @@ int parrot_voc_train_backward(const parrot_voc_cfg* cfg, const parrot_voc_train_
                               const void* saved, const float* grad_wav, int32_t B, int32_t U, const parrot_voc_train_ptrs* grads, void* ws,
                               size_t ws_bytes, void* stream);
 
+/* ---- training the multi-period discriminator (utils/vocoder/models.py:171-225 with weight norm attached; train.py:141-142, :159-163) ----
+ * MultiPeriodDiscriminator.forward and its full backward as two stateless calls shaped like the generator's: parameters are read
+ * from the DEVICE pointers given here, in torch's layout ((C_out, C_in, k, 1) is (C_out, C_in, k)); nothing is packed, cached or copied
+ * to the host, and neither call synchronises.
+ *   forward: wav (N, 1, T) f32 -- the caller stacks real and generated rows, N = 2 B.  Per period p: the tail is reflect-padded by
+ *   n_pad = p - T mod p when T mod p != 0 and the row viewed as (H, p); convs[0 .. 4) are (kernel_size, 1) convs of stride (stride, 1),
+ *   convs[4] has stride 1, each with padding (2, 0) whatever kernel_size is, bias and leaky ReLU `slope`; conv_post is (3, 1), padding
+ *   (1, 0), no activation.  The widths are 1 -> channels[0] -> ... -> channels[3] -> channels[3] -> 1.
+ *   Maps: the caller owns the six maps of every period and gets them PERIOD-MAJOR: map[i][l] is a dense (N, periods[i], C_l, H_l)
+ *   array, H_l = parrot_mpd_train_map_rows(cfg, T, i, l); torch's (N, C_l, H_l, p) is its permutation (0, 2, 3, 1), and the score the
+ *   flattened sixth map.  The maps are also what the backward reads (the leaky ReLU's mask is map > 0, the next layer's weight
+ *   gradient reads the same buffer): they must reach it unchanged.
+ *   saved (parrot_mpd_train_saved_bytes; NULL = keep nothing): every layer's weight-norm row norms and folded weight.
+ * backward: grad_maps->map[i][l] is the gradient that arrives at map[i][l] from outside, in the map's layout, or NULL for zero; the
+ *   gradient at a map is (that + the next layer's data gradient), and the sum passes the map's mask.  Outputs: the gradient of every
+ *   parameter named in `grads` (a null field is neither wanted nor computed; weight norm as in parrot_voc_train_backward) and, when
+ *   grad_wav != NULL, d wav (N, 1, T), the periods added in their order; the reflect pad's backward adds padded sample T + i into
+ *   sample T - 2 - i once, after the sample's own gradient.  With grad_wav == NULL the first layer's data gradient is not launched.
+ * Numerics: the generator's contract (exact fp32 products, fp32 accumulation in bounded chains, fp64 fixed-order sums for everything
+ * that ends in one number, no floating-point atomics, rows independent, NaN / inf propagate).  Limits (PARROT_E_INVALID, before any
+ * HIP call): 1 to 8 periods, each >= 1; N, T and the widths >= 1; kernel_size odd and <= 11; 1 <= stride <= kernel_size; T > n_pad
+ * for every period (torch refuses a reflect pad that is not smaller than its input); N p <= 65535; a null parameter or map; a
+ * workspace that is too small is PARROT_E_NOMEM. */
+#define PARROT_MPD_MAX_PERIODS 8
+#define PARROT_MPD_LAYERS 6 /* convs[0 .. 5), conv_post */
+typedef struct {
+    int32_t n_periods;
+    int32_t periods[PARROT_MPD_MAX_PERIODS]; /* reference: 2, 3, 5, 7, 11 */
+    int32_t channels[4];                     /* reference: 32, 128, 512, 1024 (hard-coded there; a field here so that tests can run narrow) */
+    int32_t kernel_size;                     /* 5 */
+    int32_t stride;                          /* 3 */
+    float slope;                             /* LRELU_SLOPE = 0.1 */
+} parrot_mpd_cfg;
+/* DEVICE pointers of every parameter, or of every gradient: layer[i][l] is discriminators.i.convs.l, l = 5: conv_post */
+typedef struct {
+    parrot_voc_layer_ptrs layer[PARROT_MPD_MAX_PERIODS][PARROT_MPD_LAYERS];
+} parrot_mpd_ptrs;
+typedef struct {
+    float* map[PARROT_MPD_MAX_PERIODS][PARROT_MPD_LAYERS];
+} parrot_mpd_maps;
+/* Rows H_l of map `layer` of period index `period` for rows of T samples; 0 beyond the limits. */
+int64_t parrot_mpd_train_map_rows(const parrot_mpd_cfg* cfg, int32_t T, int32_t period, int32_t layer);
+/* Bytes of what the forward keeps besides the maps, and of the workspace of either call (0 beyond the limits). */
+size_t parrot_mpd_train_saved_bytes(const parrot_mpd_cfg* cfg, int32_t N, int32_t T);
+size_t parrot_mpd_train_workspace_bytes(const parrot_mpd_cfg* cfg, int32_t N, int32_t T);
+int parrot_mpd_train_forward(const parrot_mpd_cfg* cfg, const parrot_mpd_ptrs* w, const float* wav, int32_t N, int32_t T,
+                             const parrot_mpd_maps* maps, void* saved, void* ws, size_t ws_bytes, void* stream);
+int parrot_mpd_train_backward(const parrot_mpd_cfg* cfg, const parrot_mpd_ptrs* w, const float* wav, const parrot_mpd_maps* maps,
+                              const void* saved, const parrot_mpd_maps* grad_maps, int32_t N, int32_t T, const parrot_mpd_ptrs* grads,
+                              float* grad_wav, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -227,6 +227,35 @@ int parrot_debug_voc_conv_dw(const float* dy, const float* x, float* dw, int32_t
 int parrot_debug_voc_wn_fwd(const float* v, const float* g, float* w, float* norm, int32_t rows, int32_t len, void* stream);
 int parrot_debug_voc_wn_bwd(const float* dw, const float* v, const float* g, const float* norm, float* dv, float* dg, int32_t rows, int32_t len,
                             void* stream);
+/* Tests: the pieces of the multi-period discriminator's training alone (csrc/mpd_train.h and the launches host_mpd_train.hip makes
+ * of tap_gemm_kernel / wgrad_kernel), on caller-owned dense DEVICE buffers whose sizes follow from the dimensions given.
+ *   conv_*   one conv over H on Z independent rows: x (Z, c_in, H_in), w (c_out, c_in, k), padding 2, stride `stride`,
+ *            H_out = (H_in + 4 - k) / stride + 1.  fwd: y (Z, c_out, H_out) = conv + bias (nullable), then the leaky ReLU when act;
+ *            dx (Z, c_in, H_in) = mask(pre + the data gradient of dy), pre and mask (Z, c_in, H_in) nullable; dw (w's shape); ws:
+ *            parrot_debug_mpd_conv_dw_workspace_bytes (0 for sizes that are not valid)
+ *   first_*  convs[0] fused with the reflect pad and the fold: wav (N, T), w (c1, k), y (N, period, c1, H_1); dx: d wav (N, T) from dy
+ *            (y's shape); dw (c1, k); ws: parrot_debug_mpd_first_dw_workspace_bytes
+ *   post_*   conv_post: x (Z, C, H), w (C, 3), y (Z, H); dx (Z, C, H) = mask(pre + w (x) dy); dw (C, 3); ws: ..._post_dw_workspace_bytes
+ * A null argument, a size below 1, an even k or k > 11, stride > k, T <= n_pad: PARROT_E_INVALID, before any launch. */
+int parrot_debug_mpd_conv_fwd(const float* x, const float* w, const float* bias, float* y, int32_t Z, int32_t c_in, int32_t c_out, int32_t k,
+                              int32_t stride, int32_t H_in, int32_t act, float slope, void* stream);
+int parrot_debug_mpd_conv_dx(const float* dy, const float* w, const float* pre, const float* mask, float slope, float* dx, int32_t Z, int32_t c_in,
+                             int32_t c_out, int32_t k, int32_t stride, int32_t H_in, void* stream);
+size_t parrot_debug_mpd_conv_dw_workspace_bytes(int32_t Z, int32_t c_in, int32_t c_out, int32_t k, int32_t stride, int32_t H_in);
+int parrot_debug_mpd_conv_dw(const float* dy, const float* x, float* dw, int32_t Z, int32_t c_in, int32_t c_out, int32_t k, int32_t stride,
+                             int32_t H_in, void* ws, size_t ws_bytes, void* stream);
+int parrot_debug_mpd_first_fwd(const float* wav, const float* w, const float* bias, float* y, int32_t N, int32_t T, int32_t period, int32_t c1,
+                               int32_t k, int32_t stride, float slope, void* stream);
+int parrot_debug_mpd_first_dx(const float* dy, const float* w, float* dwav, int32_t N, int32_t T, int32_t period, int32_t c1, int32_t k,
+                              int32_t stride, void* stream);
+size_t parrot_debug_mpd_first_dw_workspace_bytes(int32_t N, int32_t T, int32_t period, int32_t c1, int32_t k, int32_t stride);
+int parrot_debug_mpd_first_dw(const float* dy, const float* wav, float* dw, int32_t N, int32_t T, int32_t period, int32_t c1, int32_t k,
+                              int32_t stride, void* ws, size_t ws_bytes, void* stream);
+int parrot_debug_mpd_post_fwd(const float* x, const float* w, const float* bias, float* y, int32_t Z, int32_t C, int32_t H, void* stream);
+int parrot_debug_mpd_post_dx(const float* dy, const float* w, const float* pre, const float* mask, float slope, float* dx, int32_t Z, int32_t C,
+                             int32_t H, void* stream);
+size_t parrot_debug_mpd_post_dw_workspace_bytes(int32_t Z, int32_t C, int32_t H);
+int parrot_debug_mpd_post_dw(const float* dy, const float* x, float* dw, int32_t Z, int32_t C, int32_t H, void* ws, size_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -3,4 +3,7 @@ def __getattr__(name):
     if name == "TrainableCodeGenerator":
         from .vocoder_train import TrainableCodeGenerator
         return TrainableCodeGenerator
+    if name == "TrainableMultiPeriodDiscriminator":
+        from .discriminator_train import TrainableMultiPeriodDiscriminator
+        return TrainableMultiPeriodDiscriminator
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -116,6 +116,22 @@ class VocTrainPtrs(C.Structure):  # parrot_voc_train_ptrs: the parameters, or wh
                 ("rb", VocLayerPtrs * VOC_TRAIN_MAX_RB), ("conv_post", VocLayerPtrs)]
 
 
+MPD_MAX_PERIODS, MPD_LAYERS = 8, 6  # PARROT_MPD_MAX_PERIODS, PARROT_MPD_LAYERS of include/parrot_hip.h
+
+
+class MpdCfg(C.Structure):  # parrot_mpd_cfg
+    _fields_ = [("n_periods", C.c_int32), ("periods", C.c_int32 * MPD_MAX_PERIODS), ("channels", C.c_int32 * 4), ("kernel_size", C.c_int32),
+                ("stride", C.c_int32), ("slope", C.c_float)]
+
+
+class MpdPtrs(C.Structure):  # parrot_mpd_ptrs: the parameters, or where the backward writes their gradients
+    _fields_ = [("layer", (VocLayerPtrs * MPD_LAYERS) * MPD_MAX_PERIODS)]
+
+
+class MpdMaps(C.Structure):  # parrot_mpd_maps: the six maps of every period, or the gradients that arrive at them
+    _fields_ = [("map", (C.c_void_p * MPD_LAYERS) * MPD_MAX_PERIODS)]
+
+
 class GanTerm(C.Structure):  # parrot_gan_term_t: 48 bytes
     _fields_ = [("a", C.c_void_p), ("b", C.c_void_p), ("grad_a", C.c_void_p), ("grad_b", C.c_void_p), ("n", C.c_int64),
                 ("op", C.c_int32), ("reserved", C.c_int32)]
@@ -288,6 +304,24 @@ SIGNATURES = {
     "parrot_debug_voc_conv_dw": (C.c_int, [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, sz, vp]),
     "parrot_debug_voc_wn_fwd": (C.c_int, [vp, vp, vp, vp, i32, i32, vp]),
     "parrot_debug_voc_wn_bwd": (C.c_int, [vp, vp, vp, vp, vp, vp, i32, i32, vp]),
+    "parrot_mpd_train_map_rows": (C.c_int64, [C.POINTER(MpdCfg), i32, i32, i32]),
+    "parrot_mpd_train_saved_bytes": (sz, [C.POINTER(MpdCfg), i32, i32]),
+    "parrot_mpd_train_workspace_bytes": (sz, [C.POINTER(MpdCfg), i32, i32]),
+    "parrot_mpd_train_forward": (C.c_int, [C.POINTER(MpdCfg), C.POINTER(MpdPtrs), vp, i32, i32, C.POINTER(MpdMaps), vp, vp, sz, vp]),
+    "parrot_mpd_train_backward": (C.c_int, [C.POINTER(MpdCfg), C.POINTER(MpdPtrs), vp, C.POINTER(MpdMaps), vp, C.POINTER(MpdMaps), i32, i32,
+                                            C.POINTER(MpdPtrs), vp, vp, sz, vp]),
+    "parrot_debug_mpd_conv_fwd": (C.c_int, [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, f32, vp]),
+    "parrot_debug_mpd_conv_dx": (C.c_int, [vp, vp, vp, vp, f32, vp, i32, i32, i32, i32, i32, i32, vp]),
+    "parrot_debug_mpd_conv_dw_workspace_bytes": (sz, [i32, i32, i32, i32, i32, i32]),
+    "parrot_debug_mpd_conv_dw": (C.c_int, [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, sz, vp]),
+    "parrot_debug_mpd_first_fwd": (C.c_int, [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, f32, vp]),
+    "parrot_debug_mpd_first_dx": (C.c_int, [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]),
+    "parrot_debug_mpd_first_dw_workspace_bytes": (sz, [i32, i32, i32, i32, i32, i32]),
+    "parrot_debug_mpd_first_dw": (C.c_int, [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, sz, vp]),
+    "parrot_debug_mpd_post_fwd": (C.c_int, [vp, vp, vp, vp, i32, i32, i32, vp]),
+    "parrot_debug_mpd_post_dx": (C.c_int, [vp, vp, vp, vp, f32, vp, i32, i32, i32, vp]),
+    "parrot_debug_mpd_post_dw_workspace_bytes": (sz, [i32, i32, i32]),
+    "parrot_debug_mpd_post_dw": (C.c_int, [vp, vp, vp, i32, i32, i32, vp, sz, vp]),
     "parrot_debug_tap_gemm": (C.c_int, [C.POINTER(DebugTapGemmDesc), vp]),
     "parrot_debug_wgrad_workspace_bytes": (sz, [i32, i32, i32, i32]),
     "parrot_debug_wgrad": (C.c_int, [C.POINTER(DebugWgradDesc), vp, sz, vp]),

@@ -13,8 +13,9 @@
 // (the ReLU is `v < 0 ? 0 : v`).
 // The vocoder's extra fields: x_mul / x_n (TapGemmParams) and x_mul / x_T (WgradParams) read X at a stride with its own bound, for
 // the phases of a transposed conv and its gradients; mask / mslope, res and lrelu / lslope extend the epilogue by a leaky ReLU's
-// backward, a residual add and the next conv's activation.  A zero in every extra field is the base behaviour bit for bit, so a
-// caller that value-initialises the struct and fills the base fields need not know of them.
+// backward, a residual add and the next conv's activation; pre (the discriminator's training, mpd_train.h) is added before the mask:
+// the gradient that arrives at a saved map from outside joins the data gradient, and the sum passes the mask.  A zero in every extra
+// field is the base behaviour bit for bit, so a caller that value-initialises the struct and fills the base fields need not know of them.
 // The launchers are defined in tu_train_gemm.hip, which alone sees the kernel bodies (PARROT_TRAIN_GEMM_TU).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -29,8 +30,8 @@ constexpr int TG_ACC_FLUSH = 8;   // tap_gemm_kernel moves its accumulator into 
 // Y[z][m][n] = act(sum_j sum_k A_j[m][k] X[z][k][n + shift_j] + bias0[m] + bias1[m]); X is zero outside 0 <= n + shift_j < N.
 // The fields after `relu` serve the vocoder's training (voc_train.h); zero in each of them is the line above, bit for bit:
 //   X is read at column n x_mul + shift_j and is zero outside [0, x_n)  (x_mul = 0: 1; x_n = 0: N): a transposed conv's phases and its
-//   data gradient;  then, after the bias:  v = mask[z][m][n] > 0 ? v : v mslope  (a leaky ReLU's backward on its saved output),
-//   v += res[z][m][n]  (a residual), both at C's strides;  and after `relu`:  v = v > 0 ? v : v lslope  when lrelu.
+//   data gradient;  then, after the bias:  v += pre[z][m][n],  v = mask[z][m][n] > 0 ? v : v mslope  (a leaky ReLU's backward on its
+//   saved output),  v += res[z][m][n]  (a residual), all three at C's strides;  and after `relu`:  v = v > 0 ? v : v lslope  when lrelu.
 struct TapGemmParams {
     const float* A[TG_MAX_TAPS];  // tap j: A_j[m][k] at A[j] + m a_sm + k a_sk
     long x_off[TG_MAX_TAPS];      // tap j reads X[z] + x_off[j] (a column block of a wider array)
@@ -49,6 +50,7 @@ struct TapGemmParams {
     const float* res;
     int lrelu;
     float lslope;
+    const float* pre;
 };
 // part[chunk][j][m][k] = sum over the chunk's (b, t) of dY[b][m][t] X[b][k][t + shift_j]; chunk c covers r = b T + t in
 // [c TG_RCHUNK, (c + 1) TG_RCHUNK).  X is zero outside 0 <= t + shift_j < T.
@@ -144,9 +146,10 @@ __global__ __launch_bounds__(256) void tap_gemm_kernel(const TapGemmParams p) {
             float v = tot[r] + acc[r];
             if (p.bias0) v += p.bias1 ? __fadd_rn(p.bias0[m], p.bias1[m]) : p.bias0[m];
             const long o = (long)m * p.c_sm + (long)n * p.c_sn;
-            if (p.mask || p.res) {
+            if (p.mask || p.res || p.pre) {
 #pragma clang fp contract(off)  // (the product and the sum are rounded one after the other, as torch rounds them)
                 const long oz = (long)blockIdx.z * p.c_sz + o;
+                if (p.pre) v = v + p.pre[oz];
                 if (p.mask && !(p.mask[oz] > 0.f)) v = v * p.mslope;
                 if (p.res) v = v + p.res[oz];
             }

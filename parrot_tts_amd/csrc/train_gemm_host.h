@@ -1,5 +1,5 @@
-// train_gemm_host.h -- host only: the products of the three training units (host_aligner_train.hip, host_tte_train.hip,
-// host_voc_train.hip) as launches of train_gemm.h.  An activation array is described by three strides, a weight by torch's own
+// train_gemm_host.h -- host only: the products of the training units (host_aligner_train.hip, host_tte_train.hip,
+// host_voc_train.hip; host_mpd_train.hip fills the structs itself for its strided convs) as launches of train_gemm.h.  An activation array is described by three strides, a weight by torch's own
 // layout, and conv forward, data gradient and weight gradient are written once over the two; a Linear is the k = 1 conv over all its
 // rows as one batch row.  Every function returns PARROT_OK or what fail() returned.
 #pragma once
@@ -21,7 +21,7 @@ struct ConvW {
     const float* w;
     int cout, cin, k, dil, pad;
 };
-// What tap_gemm_kernel's epilogue adds to the product, in the kernel's order; all zero: nothing
+// What tap_gemm_kernel's epilogue adds to the product, in the kernel's order (pre, the last field, comes before the mask); all zero: nothing
 struct Epi {
     const float *bias0 = nullptr, *bias1 = nullptr;
     const float* mask = nullptr;
@@ -29,9 +29,10 @@ struct Epi {
     const float* res = nullptr;
     int relu = 0, lrelu = 0;
     float lslope = 0.f;
+    const float* pre = nullptr;
 };
 inline void set_epi(TapGemmParams& g, const Epi& e) {
-    g.bias0 = e.bias0; g.bias1 = e.bias1; g.mask = e.mask; g.mslope = e.mslope; g.res = e.res; g.relu = e.relu; g.lrelu = e.lrelu; g.lslope = e.lslope;
+    g.bias0 = e.bias0; g.bias1 = e.bias1; g.mask = e.mask; g.mslope = e.mslope; g.res = e.res; g.relu = e.relu; g.lrelu = e.lrelu; g.lslope = e.lslope; g.pre = e.pre;
 }
 
 // Y[b][co][t] = epi(sum_j sum_ci W[co][ci][j] X[b][ci][t + j dil - pad])

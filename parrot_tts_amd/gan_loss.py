@@ -7,7 +7,8 @@ reduction.  The losses are differentiable with respect to every tensor that requ
 with the upstream gradients formed on the device (no host synchronisation, no double backward).  ``generator_adversarial_loss``
 and ``discriminator_adversarial_loss`` are the reference trainer's sums (train.py:161-165 without the mel term, train.py:142-148)
 as one call each -- 62 terms for the generator step -- and their ``*_and_grad`` forms return values and gradients from a single
-fused call.  For torch-built discriminators: the discriminators themselves stay ``nn.Module``s."""
+fused call.  The inputs may come from torch-built discriminators or from ``discriminator_train.TrainableMultiPeriodDiscriminator``,
+whose maps are permuted views: every input is made dense once (``_dense``)."""
 from __future__ import annotations
 
 import torch

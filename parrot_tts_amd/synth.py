@@ -331,3 +331,48 @@ def synth_aligner_mel(B: int, T: int, n_mels: int, mel_len=None, seed: int = 0) 
 
 def clone_config(cfg: dict) -> dict:
     return copy.deepcopy(cfg)
+
+
+# --------------------------------------------------------------------------------------
+# multi-period discriminator
+# --------------------------------------------------------------------------------------
+def default_mpd_config() -> dict:
+    """What reference utils/vocoder/models.py:171-210 hard-codes."""
+    return {"periods": [2, 3, 5, 7, 11], "channels": [32, 128, 512, 1024], "kernel_size": 5, "stride": 3}
+
+
+def mpd_layer_shapes(cfg: dict):
+    """(key prefix, cout, cin, k) of every conv in state_dict order: per period convs.0 .. convs.4, then conv_post."""
+    c = [1] + list(cfg["channels"]) + [cfg["channels"][-1]]
+    out = []
+    for i in range(len(cfg["periods"])):
+        out += [(f"discriminators.{i}.convs.{l}", c[l + 1], c[l], cfg["kernel_size"]) for l in range(5)]
+        out.append((f"discriminators.{i}.conv_post", 1, c[5], 3))
+    return out
+
+
+def synth_mpd_state_dict(cfg: dict = None, seed: int = 1234) -> Dict[str, torch.Tensor]:
+    """Seeded ``mpd`` entry of a ``do_%08d`` checkpoint (reference utils/vocoder/train.py:187-192) with weight norm attached, the
+    reference's key order (bias, weight_g, weight_v).  fp64 draws n ~ N(0, 1) from one ``torch.Generator``, rounded to fp32:
+    ``weight_v = n / sqrt(cin k)``, ``weight_g = ||v|| (1 + 0.1 n)``, ``bias = 0.1 n``; conv_post has ``g = ||v||`` and a zero bias, so
+    scores stay of order one.  The default config's dict is 164 MB."""
+    cfg = cfg or default_mpd_config()
+    gen = torch.Generator().manual_seed(seed)
+    draw = lambda *shape: torch.randn(shape, generator=gen, dtype=torch.float64)  # noqa: E731
+    sd: Dict[str, torch.Tensor] = {}
+    for name, cout, cin, k in mpd_layer_shapes(cfg):
+        post = name.endswith("conv_post")
+        v = (draw(cout, cin, k, 1) / math.sqrt(cin * k)).to(torch.float32)
+        norm = v.double().flatten(1).norm(dim=1).reshape(-1, 1, 1, 1)
+        g = norm if post else norm * (1 + 0.1 * draw(cout, 1, 1, 1))
+        sd[name + ".bias"] = torch.zeros(cout) if post else (0.1 * draw(cout)).to(torch.float32)
+        sd[name + ".weight_g"] = g.to(torch.float32)
+        sd[name + ".weight_v"] = v
+    return sd
+
+
+def synth_mpd_batch(B: int, T: int, seed: int = 1235):
+    """``(y, y_hat)``, each (B, 1, T) fp32: 0.3 n, fp64 draws rounded to fp32."""
+    gen = torch.Generator().manual_seed(seed)
+    y, y_hat = (0.3 * torch.randn((B, 1, T), generator=gen, dtype=torch.float64) for _ in range(2))
+    return y.to(torch.float32), y_hat.to(torch.float32)
