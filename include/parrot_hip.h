@@ -787,6 +787,61 @@ int parrot_mpd_train_backward(const parrot_mpd_cfg* cfg, const parrot_mpd_ptrs* 
                               const void* saved, const parrot_mpd_maps* grad_maps, int32_t N, int32_t T, const parrot_mpd_ptrs* grads,
                               float* grad_wav, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- training the multi-scale discriminator (utils/vocoder/models.py:228-276; train.py:142-143, :160-164) ----
+ * MultiScaleDiscriminator.forward and its full backward as two stateless calls shaped like the multi-period discriminator's.
+ *   forward: wav (N, 1, T) f32, N = 2 B even: the caller stacks real rows [0, B) and generated rows [B, 2 B).  Scale i sees the
+ *   waveform after i AvgPool1d(4, 2, padding=2) (length T / 2 + 1 each time, always divided by 4).  Every scale is convs[0] (1 -> c0, 15
+ *   taps, padding 7), convs[1 .. 5] (41 taps, padding 20, strides 2, 2, 4, 4, 1, groups[l]), convs[6] (5 taps, padding 2), each with bias
+ *   and leaky ReLU `slope`, and conv_post (c6 -> 1, 3 taps, padding 1, no activation).  Weights are torch's: (C_out, C_in / groups, k).
+ *   A layer is one of: plain (v = weight), weight-normed (v, g) or spectral-normed (v = weight_orig, u, sv = the buffers weight_u and
+ *   weight_v); cfg->spectral[i] says which scales are spectral, and every layer of such a scale must carry u and sv.
+ *   Spectral norm: sigma = u^T (W v) with W = weight_orig as (C_out, C_in / groups k); the layer runs on W / sigma.  The reference calls
+ *   the discriminator once on the real and once on the generated rows, and a call in training mode starts with one power iteration
+ *   (v = normalize(W^T u), u = normalize(W v), eps 1e-12): with power_iterations = 1 the real rows run on the fold after one iteration, the
+ *   generated rows on the fold after two, and u and sv are UPDATED IN PLACE, two iterations on.  With power_iterations = 0 (eval) the
+ *   buffers are read only and both halves use one sigma.
+ *   Maps: the caller owns the eight maps of every scale, map[i][l] a dense (N, C_l, L_l) array, L_l = parrot_msd_train_map_len(cfg, T, i, l);
+ *   the score is the flattened eighth.  They are also what the backward reads and must reach it unchanged.
+ *   saved (parrot_msd_train_saved_bytes; NULL = keep nothing): the pooled waveforms, every layer's weight-norm row norms and folded
+ *   weight and, per spectral layer, both folded weights and both (u, v, sigma) triples -- the caller's buffers have moved on by the
+ *   time the backward runs.
+ * backward: grad_maps as in parrot_mpd_train_backward.  Outputs: the gradient of every parameter named in `grads` (v, g, bias; u and sv
+ *   are ignored; a null field is neither wanted nor computed) and, when grad_wav != NULL, d wav (N, 1, T): scale 0's gradient plus the
+ *   pool's backward of the scales below, chained.  Through sigma the backward treats u and v as constants:
+ *   d weight_orig = G_r / s1 - (<G_r, W> / s1^2) u1 v1^T + G_g / s2 - (<G_g, W> / s2^2) u2 v2^T.
+ * Numerics: the generator's contract.  Limits (PARROT_E_INVALID, before any HIP call): 1 to 4 scales; N even, 2 <= N <= 65534; T >= 1;
+ * widths >= 1, each a multiple of its groups; groups[0] = groups[6] = 1; power_iterations 0 or 1; every map below 2^30 elements and
+ * N L <= 65535 x 256 at the grouped layers; a null parameter or map, a spectral layer without u / sv or with g; a workspace that is
+ * too small is PARROT_E_NOMEM. */
+#define PARROT_MSD_MAX_SCALES 4
+#define PARROT_MSD_LAYERS 8 /* convs[0 .. 7), conv_post */
+typedef struct {
+    int32_t n_scales;                        /* reference: 3 */
+    int32_t spectral[PARROT_MSD_MAX_SCALES]; /* reference: 1, 0, 0 */
+    int32_t channels[7];                     /* reference: 128, 128, 256, 512, 1024, 1024, 1024 (hard-coded there; tests run narrow) */
+    int32_t groups[7];                       /* reference: 1, 4, 16, 16, 16, 16, 1 */
+    float slope;                             /* LRELU_SLOPE = 0.1 */
+} parrot_msd_cfg;
+typedef struct {
+    float *v, *g, *bias, *u, *sv;
+} parrot_msd_layer_ptrs;
+/* DEVICE pointers of every parameter, or of every gradient: layer[i][l] is discriminators.i.convs.l, l = 7: conv_post */
+typedef struct {
+    parrot_msd_layer_ptrs layer[PARROT_MSD_MAX_SCALES][PARROT_MSD_LAYERS];
+} parrot_msd_ptrs;
+typedef struct {
+    float* map[PARROT_MSD_MAX_SCALES][PARROT_MSD_LAYERS];
+} parrot_msd_maps;
+/* Length L_l of map `layer` of scale `scale` for rows of T samples; 0 beyond the limits. */
+int64_t parrot_msd_train_map_len(const parrot_msd_cfg* cfg, int32_t T, int32_t scale, int32_t layer);
+size_t parrot_msd_train_saved_bytes(const parrot_msd_cfg* cfg, int32_t N, int32_t T);
+size_t parrot_msd_train_workspace_bytes(const parrot_msd_cfg* cfg, int32_t N, int32_t T);
+int parrot_msd_train_forward(const parrot_msd_cfg* cfg, const parrot_msd_ptrs* w, const float* wav, int32_t N, int32_t T,
+                             int32_t power_iterations, const parrot_msd_maps* maps, void* saved, void* ws, size_t ws_bytes, void* stream);
+int parrot_msd_train_backward(const parrot_msd_cfg* cfg, const parrot_msd_ptrs* w, const float* wav, const parrot_msd_maps* maps,
+                              const void* saved, const parrot_msd_maps* grad_maps, int32_t N, int32_t T, const parrot_msd_ptrs* grads,
+                              float* grad_wav, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

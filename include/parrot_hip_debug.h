@@ -256,6 +256,37 @@ int parrot_debug_mpd_post_dx(const float* dy, const float* w, const float* pre, 
                              int32_t H, void* stream);
 size_t parrot_debug_mpd_post_dw_workspace_bytes(int32_t Z, int32_t C, int32_t H);
 int parrot_debug_mpd_post_dw(const float* dy, const float* x, float* dw, int32_t Z, int32_t C, int32_t H, void* ws, size_t ws_bytes, void* stream);
+/* Tests: the pieces of the multi-scale discriminator's training alone (csrc/msd_train.h), on caller-owned dense DEVICE buffers.
+ *   gconv_*  one grouped conv: x (Z, c_in, T_in), w (c_out, c_in / groups, k), padding (k - 1) / 2, stride <= 4, k odd <= 41,
+ *            T_out = (T_in - 1) / stride + 1.  fwd: y (Z, c_out, T_out) = conv + bias (nullable), then the leaky ReLU when act;
+ *            dx (Z, c_in, T_in) = mask(pre + the data gradient of dy), pre and mask nullable; dw (w's shape); ws:
+ *            parrot_debug_msd_gconv_dw_workspace_bytes (0 for sizes that are not valid)
+ *   first_*  convs[0]: wav (Z, T), w (c1, 15), y (Z, c1, T); dx: d wav (Z, T); dw (c1, 15); ws: ..._first_dw_workspace_bytes
+ *   pool_*   AvgPool1d(4, 2, padding=2): x (Z, T) -> y (Z, T / 2 + 1); bwd: dx (Z, T) from dy (Z, T / 2 + 1)
+ *   sn_fold  w (rows, cols); iterate: one power iteration on u (rows), v (cols) in place; sigma[0] = u^T (w v), wf = w / sigma;
+ *            ws: (rows + cols) floats
+ *   sn_bwd   dw = ga / sa - (<ga, w> / sa^2) ua va^T (+ the same of gb, ub, vb, sb when gb != NULL); sa, sb: one device float each;
+ *            ws: parrot_debug_msd_sn_bwd_workspace_bytes
+ * A null argument or a size outside the limits: PARROT_E_INVALID, before any launch. */
+int parrot_debug_msd_gconv_fwd(const float* x, const float* w, const float* bias, float* y, int32_t Z, int32_t c_in, int32_t c_out, int32_t groups,
+                               int32_t k, int32_t stride, int32_t T_in, int32_t act, float slope, void* stream);
+int parrot_debug_msd_gconv_dx(const float* dy, const float* w, const float* pre, const float* mask, float slope, float* dx, int32_t Z, int32_t c_in,
+                              int32_t c_out, int32_t groups, int32_t k, int32_t stride, int32_t T_in, void* stream);
+size_t parrot_debug_msd_gconv_dw_workspace_bytes(int32_t Z, int32_t c_in, int32_t c_out, int32_t groups, int32_t k, int32_t stride, int32_t T_in);
+int parrot_debug_msd_gconv_dw(const float* dy, const float* x, float* dw, int32_t Z, int32_t c_in, int32_t c_out, int32_t groups, int32_t k,
+                              int32_t stride, int32_t T_in, void* ws, size_t ws_bytes, void* stream);
+int parrot_debug_msd_first_fwd(const float* wav, const float* w, const float* bias, float* y, int32_t Z, int32_t T, int32_t c1, float slope,
+                               void* stream);
+int parrot_debug_msd_first_dx(const float* dy, const float* w, float* dwav, int32_t Z, int32_t T, int32_t c1, void* stream);
+size_t parrot_debug_msd_first_dw_workspace_bytes(int32_t Z, int32_t T, int32_t c1);
+int parrot_debug_msd_first_dw(const float* dy, const float* wav, float* dw, int32_t Z, int32_t T, int32_t c1, void* ws, size_t ws_bytes, void* stream);
+int parrot_debug_msd_pool_fwd(const float* x, float* y, int32_t Z, int32_t T, void* stream);
+int parrot_debug_msd_pool_bwd(const float* dy, float* dx, int32_t Z, int32_t T, void* stream);
+int parrot_debug_msd_sn_fold(const float* w, float* u, float* v, int32_t rows, int32_t cols, int32_t iterate, float* wf, float* sigma, void* ws,
+                             size_t ws_bytes, void* stream);
+size_t parrot_debug_msd_sn_bwd_workspace_bytes(int32_t rows, int32_t cols);
+int parrot_debug_msd_sn_bwd(const float* ga, const float* gb, const float* w, const float* ua, const float* va, const float* sa, const float* ub,
+                            const float* vb, const float* sb, float* dw, int32_t rows, int32_t cols, void* ws, size_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -6,4 +6,7 @@ def __getattr__(name):
     if name == "TrainableMultiPeriodDiscriminator":
         from .discriminator_train import TrainableMultiPeriodDiscriminator
         return TrainableMultiPeriodDiscriminator
+    if name == "TrainableMultiScaleDiscriminator":
+        from .msd_train import TrainableMultiScaleDiscriminator
+        return TrainableMultiScaleDiscriminator
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

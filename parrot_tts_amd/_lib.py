@@ -132,6 +132,26 @@ class MpdMaps(C.Structure):  # parrot_mpd_maps: the six maps of every period, or
     _fields_ = [("map", (C.c_void_p * MPD_LAYERS) * MPD_MAX_PERIODS)]
 
 
+MSD_MAX_SCALES, MSD_LAYERS = 4, 8  # PARROT_MSD_MAX_SCALES, PARROT_MSD_LAYERS of include/parrot_hip.h
+
+
+class MsdCfg(C.Structure):  # parrot_msd_cfg
+    _fields_ = [("n_scales", C.c_int32), ("spectral", C.c_int32 * MSD_MAX_SCALES), ("channels", C.c_int32 * 7), ("groups", C.c_int32 * 7),
+                ("slope", C.c_float)]
+
+
+class MsdLayerPtrs(C.Structure):  # parrot_msd_layer_ptrs: v (weight, weight_v or weight_orig), g, bias, and a spectral layer's buffers u, sv
+    _fields_ = [("v", C.c_void_p), ("g", C.c_void_p), ("bias", C.c_void_p), ("u", C.c_void_p), ("sv", C.c_void_p)]
+
+
+class MsdPtrs(C.Structure):  # parrot_msd_ptrs: the parameters, or where the backward writes their gradients
+    _fields_ = [("layer", (MsdLayerPtrs * MSD_LAYERS) * MSD_MAX_SCALES)]
+
+
+class MsdMaps(C.Structure):  # parrot_msd_maps: the eight maps of every scale, or the gradients that arrive at them
+    _fields_ = [("map", (C.c_void_p * MSD_LAYERS) * MSD_MAX_SCALES)]
+
+
 class GanTerm(C.Structure):  # parrot_gan_term_t: 48 bytes
     _fields_ = [("a", C.c_void_p), ("b", C.c_void_p), ("grad_a", C.c_void_p), ("grad_b", C.c_void_p), ("n", C.c_int64),
                 ("op", C.c_int32), ("reserved", C.c_int32)]
@@ -322,6 +342,25 @@ SIGNATURES = {
     "parrot_debug_mpd_post_dx": (C.c_int, [vp, vp, vp, vp, f32, vp, i32, i32, i32, vp]),
     "parrot_debug_mpd_post_dw_workspace_bytes": (sz, [i32, i32, i32]),
     "parrot_debug_mpd_post_dw": (C.c_int, [vp, vp, vp, i32, i32, i32, vp, sz, vp]),
+    "parrot_msd_train_map_len": (C.c_int64, [C.POINTER(MsdCfg), i32, i32, i32]),
+    "parrot_msd_train_saved_bytes": (sz, [C.POINTER(MsdCfg), i32, i32]),
+    "parrot_msd_train_workspace_bytes": (sz, [C.POINTER(MsdCfg), i32, i32]),
+    "parrot_msd_train_forward": (C.c_int, [C.POINTER(MsdCfg), C.POINTER(MsdPtrs), vp, i32, i32, i32, C.POINTER(MsdMaps), vp, vp, sz, vp]),
+    "parrot_msd_train_backward": (C.c_int, [C.POINTER(MsdCfg), C.POINTER(MsdPtrs), vp, C.POINTER(MsdMaps), vp, C.POINTER(MsdMaps), i32, i32,
+                                            C.POINTER(MsdPtrs), vp, vp, sz, vp]),
+    "parrot_debug_msd_gconv_fwd": (C.c_int, [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, f32, vp]),
+    "parrot_debug_msd_gconv_dx": (C.c_int, [vp, vp, vp, vp, f32, vp, i32, i32, i32, i32, i32, i32, i32, vp]),
+    "parrot_debug_msd_gconv_dw_workspace_bytes": (sz, [i32, i32, i32, i32, i32, i32, i32]),
+    "parrot_debug_msd_gconv_dw": (C.c_int, [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, sz, vp]),
+    "parrot_debug_msd_first_fwd": (C.c_int, [vp, vp, vp, vp, i32, i32, i32, f32, vp]),
+    "parrot_debug_msd_first_dx": (C.c_int, [vp, vp, vp, i32, i32, i32, vp]),
+    "parrot_debug_msd_first_dw_workspace_bytes": (sz, [i32, i32, i32]),
+    "parrot_debug_msd_first_dw": (C.c_int, [vp, vp, vp, i32, i32, i32, vp, sz, vp]),
+    "parrot_debug_msd_pool_fwd": (C.c_int, [vp, vp, i32, i32, vp]),
+    "parrot_debug_msd_pool_bwd": (C.c_int, [vp, vp, i32, i32, vp]),
+    "parrot_debug_msd_sn_fold": (C.c_int, [vp, vp, vp, i32, i32, i32, vp, vp, vp, sz, vp]),
+    "parrot_debug_msd_sn_bwd_workspace_bytes": (sz, [i32, i32]),
+    "parrot_debug_msd_sn_bwd": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, sz, vp]),
     "parrot_debug_tap_gemm": (C.c_int, [C.POINTER(DebugTapGemmDesc), vp]),
     "parrot_debug_wgrad_workspace_bytes": (sz, [i32, i32, i32, i32]),
     "parrot_debug_wgrad": (C.c_int, [C.POINTER(DebugWgradDesc), vp, sz, vp]),

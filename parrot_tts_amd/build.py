@@ -1,6 +1,6 @@
 """Build libparrot_hip.so in-tree with hipcc for gfx950 (cross-compiles without a GPU).  Every csrc/*.hip is one translation unit,
 compiled in parallel, then linked: host_*.hip hold the C ABI, one unit per subsystem (three for the vocoder, host_voc*.hip, around voc.h;
-shared declarations in host_common.h; the four host_*_train.hip fill their matrix products through train_gemm_host.h), tu_*.hip
+shared declarations in host_common.h; the five host_*_train.hip fill their matrix products through train_gemm_host.h), tu_*.hip
 instantiate the kernel templates (tu_train_gemm.hip: the fp32 tap-GEMM kernels all four training paths run on)."""
 from __future__ import annotations
 

@@ -1,5 +1,5 @@
 // train_gemm_host.h -- host only: the products of the training units (host_aligner_train.hip, host_tte_train.hip,
-// host_voc_train.hip; host_mpd_train.hip fills the structs itself for its strided convs) as launches of train_gemm.h.  An activation array is described by three strides, a weight by torch's own
+// host_voc_train.hip; host_mpd_train.hip fills the structs itself for its strided convs; host_msd_train.hip uses conv_fwd / _dx / _dw for its one dense conv) as launches of train_gemm.h.  An activation array is described by three strides, a weight by torch's own
 // layout, and conv forward, data gradient and weight gradient are written once over the two; a Linear is the k = 1 conv over all its
 // rows as one batch row.  Every function returns PARROT_OK or what fail() returned.
 #pragma once

@@ -14,7 +14,8 @@ The library keeps a map period-major, (N, p, C, H); what is returned are views o
 consumer that wants dense memory (``gan_loss``) copies it once, and a score is the flattened copy of the sixth map.  The maps handed
 out are the buffers the backward reads: autograd's version check refuses a backward after one of them was written in place.
 Nothing accumulates atomically, and ``torch.use_deterministic_algorithms(True)`` is supported.  There is no CPU path: a CPU tensor
-raises.  The multi-scale discriminator (spectral norm, grouped convs) is not here: ``use_spectral_norm=True`` raises."""
+raises.  The multi-scale discriminator (spectral norm, grouped convs) is ``msd_train.TrainableMultiScaleDiscriminator``;
+``use_spectral_norm=True`` raises here."""
 from __future__ import annotations
 
 import ctypes as C
@@ -170,8 +171,8 @@ class TrainableMultiPeriodDiscriminator(nn.Module):
                  use_spectral_norm: bool = False):
         super().__init__()
         if use_spectral_norm:
-            raise NotImplementedError("TrainableMultiPeriodDiscriminator: spectral norm is the multi-scale discriminator's (MSD), "
-                                      "which is not trainable on the device yet")
+            raise NotImplementedError("TrainableMultiPeriodDiscriminator: spectral norm is the multi-scale discriminator's (MSD): "
+                                      "see parrot_tts_amd.msd_train.TrainableMultiScaleDiscriminator")
         periods, channels = [int(p) for p in periods], [int(c) for c in channels]
         if not 1 <= len(periods) <= _lib.MPD_MAX_PERIODS or len(channels) != 4:
             raise ValueError(f"TrainableMultiPeriodDiscriminator: 1 to {_lib.MPD_MAX_PERIODS} periods and four channel widths")

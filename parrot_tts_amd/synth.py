@@ -376,3 +376,53 @@ def synth_mpd_batch(B: int, T: int, seed: int = 1235):
     gen = torch.Generator().manual_seed(seed)
     y, y_hat = (0.3 * torch.randn((B, 1, T), generator=gen, dtype=torch.float64) for _ in range(2))
     return y.to(torch.float32), y_hat.to(torch.float32)
+
+
+def default_msd_config() -> dict:
+    """What reference utils/vocoder/models.py:228-258 hard-codes: the widths and group counts of convs[0 .. 7) of every DiscriminatorS
+    (kernel sizes 15, 41 x 5, 5 and strides 1, 2, 2, 4, 4, 1, 1 are fixed), three scales, spectral norm on the first."""
+    return {"channels": [128, 128, 256, 512, 1024, 1024, 1024], "groups": [1, 4, 16, 16, 16, 16, 1], "n_scales": 3}
+
+
+MSD_KERNELS = (15, 41, 41, 41, 41, 41, 5)
+
+
+def msd_layer_shapes(cfg: dict):
+    """(key prefix, cout, cin / groups, k) of every conv in state_dict order: per scale convs.0 .. convs.6, then conv_post."""
+    c = [1] + list(cfg["channels"])
+    out = []
+    for i in range(cfg["n_scales"]):
+        out += [(f"discriminators.{i}.convs.{l}", c[l + 1], c[l] // cfg["groups"][l], MSD_KERNELS[l]) for l in range(7)]
+        out.append((f"discriminators.{i}.conv_post", 1, c[7], 3))
+    return out
+
+
+def synth_msd_state_dict(cfg: dict = None, seed: int = 1234) -> Dict[str, torch.Tensor]:
+    """Seeded ``msd`` entry of a ``do_%08d`` checkpoint (reference utils/vocoder/train.py:187-192), the reference's key order.
+    fp64 draws n ~ N(0, 1) from one ``torch.Generator``, rounded to fp32.  Discriminator 0 (spectral norm): ``bias = 0.1 n``,
+    ``weight_orig = n / sqrt(cin_g k)``, ``weight_u`` and ``weight_v`` unit-norm normals FAR FROM CONVERGED, as a fresh constructor
+    leaves them, so that sigma after one power iteration and after two differ visibly; conv_post has a zero bias.  Discriminators 1
+    and up (weight norm): as ``synth_mpd_state_dict``.  The default config's dict is 118 MB."""
+    cfg = cfg or default_msd_config()
+    gen = torch.Generator().manual_seed(seed)
+    draw = lambda *shape: torch.randn(shape, generator=gen, dtype=torch.float64)  # noqa: E731
+    sd: Dict[str, torch.Tensor] = {}
+    for name, cout, cin, k in msd_layer_shapes(cfg):
+        post = name.endswith("conv_post")
+        w = (draw(cout, cin, k) / math.sqrt(cin * k)).to(torch.float32)
+        sd[name + ".bias"] = torch.zeros(cout) if post else (0.1 * draw(cout)).to(torch.float32)
+        if name.startswith("discriminators.0."):
+            u, v = draw(cout), draw(cin * k)
+            sd[name + ".weight_orig"] = w
+            sd[name + ".weight_u"] = (u / u.norm()).to(torch.float32)
+            sd[name + ".weight_v"] = (v / v.norm()).to(torch.float32)
+        else:
+            norm = w.double().flatten(1).norm(dim=1).reshape(-1, 1, 1)
+            sd[name + ".weight_g"] = (norm if post else norm * (1 + 0.1 * draw(cout, 1, 1))).to(torch.float32)
+            sd[name + ".weight_v"] = w
+    return sd
+
+
+def synth_msd_batch(B: int, T: int, seed: int = 1235):
+    """``(y, y_hat)``, each (B, 1, T) fp32: 0.3 n, fp64 draws rounded to fp32."""
+    return synth_mpd_batch(B, T, seed)
