@@ -684,6 +684,38 @@ int parrot_gan_loss(const parrot_gan_term_t* terms, int32_t K, const double* wei
                     double* term_out /* device, K, nullable */, float* total /* device, 1, nullable */, void* ws, size_t ws_bytes,
                     void* stream);
 
+/* ---- fused multi-tensor AdamW (torch.optim.AdamW without amsgrad; utils/vocoder/train.py:80-82, 151, 168) ----
+ * One call updates a whole parameter group: every tensor's p, m (exp_avg) and v (exp_avg_sq) from its gradient g, each array read
+ * once and written once, in as few launches as ceil(K / parrot_adamw_max_tensors()).  Stateless: no handle, no device allocation,
+ * no copy, no host synchronisation; the table travels in the kernel arguments.  The update is this rule, every line one correctly
+ * rounded fp32 operation and nothing contracted:
+ *   host, in double, each rounded to fp32 once:
+ *     decay = 1 - lr wd    w1 = 1 - beta1    b2 = beta2    w2 = 1 - beta2    e = eps
+ *     per tensor:  ns = -lr / (1 - beta1^step)    rs = sqrt(1 - beta2^step)
+ *   device, per element:
+ *     p <- p decay;  m <- m + (g - m) w1;  v <- v b2 + (g w2) g;  d <- sqrt(v) / rs + e;  p <- p + ns (m / d)
+ * `step` is the tensor's step count AFTER this update (>= 1), per tensor as torch keeps it per parameter.  g is read only.  The
+ * arrays are dense fp32 at any 4-byte alignment (16-byte accesses where all four bases allow them); nothing outside [0, n) is read
+ * or written; a tensor with n == 0 is skipped.  An element's result depends on its own p, g, m, v and the scalars only: two calls
+ * agree bit for bit.  NaN / inf propagate; there is no status word.
+ * PARROT_E_INVALID, before any HIP call: a null table with K > 0, K < 0, a null pointer, n < 0, step < 1, lr < 0, eps < 0,
+ * weight_decay < 0, a beta outside [0, 1), two of a tensor's four pointers equal. */
+typedef struct {
+    float* p;
+    const float* g;
+    float* m;
+    float* v;
+    int64_t n;
+    int64_t step;
+} parrot_adamw_tensor_t; /* 48 bytes */
+/* t: HOST array of K tensors with DEVICE pointers inside */
+int parrot_adamw_step(const parrot_adamw_tensor_t* t, int32_t K, double lr, double beta1, double beta2, double eps, double weight_decay,
+                      void* stream);
+/* elements one block updates */
+int32_t parrot_adamw_chunk(void);
+/* tensors one launch's by-value table holds */
+int32_t parrot_adamw_max_tensors(void);
+
 /* ---- training the vocoder's generator (utils/vocoder/models.py:69-169 with weight norm attached; train.py:131-168) ----
  * CodeGenerator.forward and its full backward as two stateless calls shaped like the TTE's.  Every parameter is read from the DEVICE
  * pointer given here, in torch's layout, through strides: nothing is packed, cached or copied to the host, neither call synchronises,

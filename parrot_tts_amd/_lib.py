@@ -157,6 +157,10 @@ class GanTerm(C.Structure):  # parrot_gan_term_t: 48 bytes
                 ("op", C.c_int32), ("reserved", C.c_int32)]
 
 
+class AdamwTensor(C.Structure):  # parrot_adamw_tensor_t: 48 bytes
+    _fields_ = [("p", C.c_void_p), ("g", C.c_void_p), ("m", C.c_void_p), ("v", C.c_void_p), ("n", C.c_int64), ("step", C.c_int64)]
+
+
 DEBUG_MAX_TAPS = 5  # PARROT_DEBUG_MAX_TAPS of include/parrot_hip_debug.h
 
 
@@ -373,6 +377,9 @@ SIGNATURES = {
     "parrot_gan_loss_tile": (i32, []),
     "parrot_gan_loss_workspace_bytes": (sz, [C.POINTER(GanTerm), i32]),
     "parrot_gan_loss": (C.c_int, [C.POINTER(GanTerm), i32, vp, C.c_double, vp, vp, vp, sz, vp]),
+    "parrot_adamw_step": (C.c_int, [C.POINTER(AdamwTensor), i32, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, vp]),
+    "parrot_adamw_chunk": (i32, []),
+    "parrot_adamw_max_tensors": (i32, []),
 }
 
 _lib = None

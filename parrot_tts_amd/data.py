@@ -205,6 +205,82 @@ class CodeDataset(torch.utils.data.Dataset):
         return feats, audio, str(filename), None
 
 
+class SegmentCodeDataset(torch.utils.data.Dataset):
+    """The TRAINING side of reference utils/vocoder/dataset.py:145-254: per item a random ``segment_size`` window of the audio with
+    the units below it, ``(feats, audio (segment_size,) fp32, filename, None)``.
+
+    As the reference: the wav on the int16 scale, optional ``pad``, ``peak_normalize(audio / 32768) * 0.95``, the trim to
+    ``min(len(audio) // code_hop_size, len(code))`` whole units, audio and code doubled (``np.hstack``) while the audio is shorter
+    than a segment, and ``_sample_interval`` (:182-202): the hops, their lcm, ``randint(0, N // lcm - seq_len // lcm)``.  The draws
+    come from a private ``random.Random(1234)`` made here: the sequence of the reference's global ``random.seed(1234)``, which other
+    users of ``random`` cannot disturb (``rng_state`` / ``set_rng_state`` carry it through a checkpoint).  The mel target is not
+    made per item on the CPU (the 4th element is None): the trainer forms it per batch on the device.  The speaker table is the
+    reference's, sorted from the names in the manifest; ``spkr_to_id=`` overrides it."""
+
+    def __init__(self, training_files, segment_size, code_hop_size=320, *unused, sampling_rate=16000, multispkr=False, pad=None,
+                 spkr_to_id=None, **kw):
+        import random
+        self.audio_files, self.codes = training_files
+        self.segment_size, self.code_hop_size, self.sampling_rate = int(segment_size), int(code_hop_size), sampling_rate
+        if self.segment_size <= 0:
+            raise ValueError("SegmentCodeDataset: segment_size must be positive (whole utterances: CodeDataset with segment_size = -1)")
+        self.multispkr, self.pad = multispkr, pad
+        self._random = random.Random(1234)  # dataset.py:150
+        if self.multispkr:
+            if spkr_to_id is not None:
+                self.spkr_to_id = dict(spkr_to_id)
+                self.id_to_spkr = sorted(self.spkr_to_id, key=self.spkr_to_id.get)
+            else:
+                self.id_to_spkr = sorted({parse_speaker(f, self.multispkr) for f in self.audio_files})
+                self.spkr_to_id = {k: v for v, k in enumerate(self.id_to_spkr)}
+
+    def __len__(self):
+        return len(self.audio_files)
+
+    def rng_state(self):
+        return self._random.getstate()
+
+    def set_rng_state(self, state) -> None:
+        self._random.setstate(state)
+
+    def _get_spkr(self, idx) -> np.ndarray:
+        return np.asarray([self.spkr_to_id[parse_speaker(self.audio_files[idx], self.multispkr)]], dtype=np.int64)
+
+    def _sample_interval(self, seqs, seq_len=None):
+        """dataset.py:182-202"""
+        N = max(v.shape[-1] for v in seqs)
+        if seq_len is None:
+            seq_len = self.segment_size
+        hops = [N // v.shape[-1] for v in seqs]
+        lcm = int(np.lcm.reduce(hops))
+        start_step = self._random.randint(0, N // lcm - seq_len // lcm)
+        out = []
+        for v, hop in zip(seqs, hops):
+            start, end = start_step * (lcm // hop), (start_step + seq_len // lcm) * (lcm // hop)
+            out.append(v[..., start:end])
+        return out
+
+    def __getitem__(self, index):
+        filename = self.audio_files[index]
+        audio, _ = load_wav_int16_scale(filename)
+        if self.pad:
+            audio = np.pad(audio, (0, self.pad - (audio.shape[-1] % self.pad)), "constant", constant_values=0)
+        audio = peak_normalize(audio / 32768.0) * 0.95              # dataset.py:212-213
+        code = np.asarray(self.codes[index], dtype=np.int64)
+        n = min(audio.shape[0] // self.code_hop_size, code.shape[0])  # :221-223
+        code, audio = code[:n], audio[: n * self.code_hop_size]
+        if n == 0:
+            raise ValueError(f"{filename}: no whole unit of audio")
+        while audio.shape[0] < self.segment_size:                   # :226-228
+            audio, code = np.hstack([audio, audio]), np.hstack([code, code])
+        audio = torch.from_numpy(audio.astype(np.float32)).unsqueeze(0)  # torch.FloatTensor(audio), :230
+        audio, code = self._sample_interval([audio, code])
+        feats = {"code": code}
+        if self.multispkr:
+            feats["spkr"] = self._get_spkr(index)
+        return feats, audio.squeeze(0), str(filename), None
+
+
 def mel_spectrogram(*args, **kwargs):
     """reference utils/vocoder/dataset.py:44-64 is a training-loss component (and the ``_gt`` mel of the driver): out of scope."""
     raise NotImplementedError("parrot_tts_amd covers the synthesis path only; mel_spectrogram is a training component")
